@@ -15,9 +15,15 @@ batch on its shard, and the per-shard top-k lists are merged after ONE RCCL all-
                            `work_rate` (query*rows/s) is the number that scales;
   --scale queries:         the corpus stays --rows in total, each rank holds rows/N of it and the batch grows to
                            N x --batch.
-`--mode graph` measures the traversal kernel as the primary (builds the graph over --rows first; minutes at 10M).  The
-default flat run adds a SECONDARY traversal measurement on the first --graph-rows rows (reference defaults T=4, L=500).
+`--mode graph` measures the traversal kernel as the primary (builds the graph over --rows first; minutes at 10M).
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time the --steps steps, print the line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the roofline of the timed launches).  `--full` adds everything else the line
+can carry, each leg after the timed region: recall@10 of the last batch against exact scans, the end-to-end (host -> host)
+repetition, the clock / power leg, the live PMC traffic of the dominant launch, a SECONDARY traversal measurement on the first
+--graph-rows rows (reference defaults T=4, L=500), the reference's CPU baseline and the further BASELINE configs (--configs).
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -130,6 +136,28 @@ def pmc_traffic(args, kernel_substr, want_rows_hint):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20   # (data; below 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, one DIR/<name>.npy each - integer arrays as float64
+    (exact: ids < 2^53), floating ones as float32.  All have one row per query; when together they exceed DUMP_LIMIT_BYTES, the same seeded sample of
+    rows is kept from each and its row numbers are written as DIR/query_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    rows = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in host.values())
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        host = {name: a[keep] for name, a in host.items()}
+        host["query_rows"] = keep.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def traffic_ref(key):
     import hashlib
     r = dict(TRAFFIC_REF[key])
@@ -145,6 +173,10 @@ from bench_legs import (HBM_PEAK_GBS, HBM_GATHER_CEILING_GBS, MFMA_F16_PEAK_TF, 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every leg beside the headline (recall check, end to end, clock / power, "
+                    "live PMC traffic, secondary traversal, CPU baseline, --configs); off: the headline step alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the ids / distances (/ counts) the last timed step returned as DIR/<name>.npy "
+                    "(float64 / float32; at most 64 MB, a seeded sample of the queries beyond that)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows per GPU (--scale rows) or in total (--scale queries)")
@@ -228,13 +260,16 @@ def main_inproc(args):
     elapsed = time.perf_counter() - t0
     st = grp.stats()
     main_ms = grp.kernel_times(64)[-args.steps:]
-    got = ids.cpu().numpy().copy()
-    nrec = min(args.recall_queries, b)
-    g = (torch.empty((nrec, k), dtype=torch.int64, device=dev0), torch.empty((nrec, k), dtype=torch.float32, device=dev0), torch.empty((nrec,), dtype=torch.int32, device=dev0))
-    torch.cuda.synchronize()
-    grp.search(queries[-1][:nrec], k, out=g, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM)
-    grp.synchronize()
-    recall = recall_of(got[:nrec], g[0].cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": ids, "distances": dd, "counts": cnt})
+    recall, nrec = None, min(args.recall_queries, b)
+    if args.full:
+        got = ids.cpu().numpy().copy()
+        g = (torch.empty((nrec, k), dtype=torch.int64, device=dev0), torch.empty((nrec, k), dtype=torch.float32, device=dev0), torch.empty((nrec,), dtype=torch.int32, device=dev0))
+        torch.cuda.synchronize()
+        grp.search(queries[-1][:nrec], k, out=g, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM)
+        grp.synchronize()
+        recall = recall_of(got[:nrec], g[0].cpu().numpy())
     qps = b * args.steps / elapsed
     kernel_ms = float(np.mean(main_ms)) if main_ms else 0.0
     bits = int(st.get("main_kernel_bits", 0))
@@ -249,7 +284,7 @@ def main_inproc(args):
         "metric": "QPS @ recall@10>=0.999, 10Mx768 L2", "value": qps, "unit": "queries/s", "n_gpus": G, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32 (exact fp32 distances; %d-bit matrix pass as a lower-bound filter, survivors re-ranked in fp32)" % bits, "data": "synthetic",
-        "recall_at_10": recall, "recall_check": {"queries": nrec, "ground_truth": "exact fp32 stream scan through the same shard group"},
+        "recall_at_10": recall, "recall_check": {"queries": nrec, "ground_truth": "exact fp32 stream scan through the same shard group"} if recall is not None else None,
         "config": {"workload": "%dM x %d L2 exact flat scan, k=%d, batch=%d per step, %d rows per GPU, %d GPU(s), rows_total=%d, ONE process: eps_index_create_sharded%s"
                                % ((n * G) // 1_000_000, d, k, b, n, G, n * G, backend_note),
                    "mode": "flat", "engine": args.engine, "parallelism": "in-process shard group x%d: row-hash shards, peer-to-peer push of packed top-k, merge on device 0" % G},
@@ -473,12 +508,14 @@ def main():
         xchg_us = mbox.times_us(64)[-args.steps:]
     elif xchg is not None:   # (all-gather | merge)
         xchg_us = xchg.times_us(64)[-args.steps:]
+    if args.dump_outputs and rank == 0:   # (what the caller of the timed path received in its last step; N > 1: the merged lists)
+        dump_outputs(args.dump_outputs, dict(ids=out_i, distances=out_d, **({"counts": cnt} if world == 1 else {})))
 
     # ---- the same steps END TO END ("QPS end-to-end including H2D of queries and D2H of results"; the reference's entry takes a
     # host vector per call, table_mvp.cpp:359-380): every batch starts in host memory and its ids / distances end in host memory,
     # inside the timed region.  `value` stays the device-resident rate (the contract: inputs resident in HBM); this one is reported beside it.
     e2e = None
-    if args.e2e:
+    if args.full and args.e2e:
         # Through the C ABI's own host path: eps_index_search with HOST query and result pointers - the library copies the batch up, searches, copies
         # the ids / distances down, inside the call (csrc/index.cpp) - exactly what the drop-in's VecSearchExecutor hands it.  Staging by the caller
         # on a second stream was measured and dropped (scripts/lab/e2e_dbg.py; a two- and a three-slot form of this loop at 10M x 768):
@@ -519,7 +556,7 @@ def main():
                        "inside the timed region; no caller-side staging (see the comment in bench.py for the staged form that measured worse)"
                        % ((" and result", "") if world == 1 else ("", ", all-gather, merge"))}
     # clock and power under this workload (N = 1, after the timed region): the filter kernel runs against the board's power limit
-    power = power_leg(torch, step, queries, args.power_seconds, local_rank) if (world == 1 and rank == 0 and args.power_seconds > 0) else None
+    power = power_leg(torch, step, queries, args.power_seconds, local_rank) if (args.full and world == 1 and rank == 0 and args.power_seconds > 0) else None
 
     # ---- N > 1: what proves that N ranks on N devices took part (the driver's SCALE run cannot be watched from here)
     ranks_info = None
@@ -541,43 +578,45 @@ def main():
     # of the library, itself pinned to the oracle by the tests) for --recall-queries queries, and a torch fp32 scan for 16
     nrec = min(args.recall_queries, b)
     qlast = queries[-1]
-    g_ids = torch.empty((nrec, k), dtype=torch.int64, device=dev)
-    g_dd = torch.empty((nrec, k), dtype=torch.float32, device=dev)
-    g_cnt = torch.empty((nrec,), dtype=torch.int32, device=dev)
-    ix.search(qlast[:nrec], k, out=(g_ids, g_dd, g_cnt), mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM)
-    ix.synchronize()
-    if world > 1:
-        gp = torch.empty(((nrec * k * 12 + 7) // 8 * 8,), dtype=torch.uint8, device=dev)
-        gp[: nrec * k * 8] = g_ids.view(torch.uint8).flatten()
-        gp[nrec * k * 8: nrec * k * 12] = g_dd.view(torch.uint8).flatten()
-        gg = torch.empty((world, gp.numel()), dtype=torch.uint8, device=dev)
-        all_gather(gg, gp)
-        t_d = torch.empty((nrec, k), dtype=torch.float32, device=dev)
-        t_i = torch.empty((nrec, k), dtype=torch.int64, device=dev)
-        amd.merge_topk_packed(gg, gp.numel(), nrec * k * 8, world, nrec, k, t_d, t_i, device=local_rank, stream=stream)
-        torch.cuda.synchronize()
-        g_ids = t_i
-    gt = g_ids.cpu().numpy()
-    recall = recall_of(got_i[:nrec].cpu().numpy(), gt)
-    ntorch = min(16, nrec)
-    torch_hits = 0
-    for qi in range(ntorch):
-        td, ti = exact_topk_torch(torch, X, qlast[qi], k, rank, world)
+    recall, gt, gt_vs_torch, ntorch = None, None, None, None
+    if args.full:
+        g_ids = torch.empty((nrec, k), dtype=torch.int64, device=dev)
+        g_dd = torch.empty((nrec, k), dtype=torch.float32, device=dev)
+        g_cnt = torch.empty((nrec,), dtype=torch.int32, device=dev)
+        ix.search(qlast[:nrec], k, out=(g_ids, g_dd, g_cnt), mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM)
+        ix.synchronize()
         if world > 1:
-            ad = torch.empty((world, k), dtype=torch.float32, device=dev)
-            ai = torch.empty((world, k), dtype=torch.int64, device=dev)
-            all_gather(ad, td.contiguous())
-            all_gather(ai, ti.contiguous())
-            o = torch.argsort(ad.flatten(), stable=True)[:k]
-            ti = ai.flatten()[o]
-        torch_hits += len(set(ti.tolist()) & set(gt[qi].tolist()))
-    gt_vs_torch = torch_hits / float(ntorch * k)
+            gp = torch.empty(((nrec * k * 12 + 7) // 8 * 8,), dtype=torch.uint8, device=dev)
+            gp[: nrec * k * 8] = g_ids.view(torch.uint8).flatten()
+            gp[nrec * k * 8: nrec * k * 12] = g_dd.view(torch.uint8).flatten()
+            gg = torch.empty((world, gp.numel()), dtype=torch.uint8, device=dev)
+            all_gather(gg, gp)
+            t_d = torch.empty((nrec, k), dtype=torch.float32, device=dev)
+            t_i = torch.empty((nrec, k), dtype=torch.int64, device=dev)
+            amd.merge_topk_packed(gg, gp.numel(), nrec * k * 8, world, nrec, k, t_d, t_i, device=local_rank, stream=stream)
+            torch.cuda.synchronize()
+            g_ids = t_i
+        gt = g_ids.cpu().numpy()
+        recall = recall_of(got_i[:nrec].cpu().numpy(), gt)
+        ntorch = min(16, nrec)
+        torch_hits = 0
+        for qi in range(ntorch):
+            td, ti = exact_topk_torch(torch, X, qlast[qi], k, rank, world)
+            if world > 1:
+                ad = torch.empty((world, k), dtype=torch.float32, device=dev)
+                ai = torch.empty((world, k), dtype=torch.int64, device=dev)
+                all_gather(ad, td.contiguous())
+                all_gather(ai, ti.contiguous())
+                o = torch.argsort(ad.flatten(), stable=True)[:k]
+                ti = ai.flatten()[o]
+            torch_hits += len(set(ti.tolist()) & set(gt[qi].tolist()))
+        gt_vs_torch = torch_hits / float(ntorch * k)
 
     # ---- secondary: the traversal kernel at the reference's defaults on a device-built graph of the first rows
     secondary = None
     graph_for_cpu = None
     ix2 = None
-    if args.mode == "flat" and world == 1 and args.graph_rows and args.graph_rows <= n:
+    if args.full and args.mode == "flat" and world == 1 and args.graph_rows and args.graph_rows <= n:
         gn = args.graph_rows
         ix2 = amd.GpuIndex(d, args.metric, device=local_rank)
         ix2.set_stream(stream)
@@ -613,7 +652,7 @@ def main():
             off, nbr, nav = ix2.get_graph()
             graph_for_cpu = (off, nbr, nav, gn, ggt)
 
-    if args.mode == "graph" and world == 1 and args.cpu_seconds > 0:
+    if args.full and args.mode == "graph" and world == 1 and args.cpu_seconds > 0:
         off, nbr, nav = ix.get_graph()
         graph_for_cpu = (off, nbr, nav, n, gt)     # the CPU graph leg searches the same device-built graph
 
@@ -657,7 +696,7 @@ def main():
             roof = {"bound": "hbm", "kernel": "flat_scan_kernel", "achieved": alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms else None,
                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None}
         roof["frac"] = (roof["achieved"] / roof["peak"]) if roof["achieved"] else None
-        if used_mfma and args.mode == "flat" and world == 1 and args.pmc and n >= 5_000_000 and not args.inproc:
+        if args.full and used_mfma and args.mode == "flat" and world == 1 and args.pmc and n >= 5_000_000 and not args.inproc:
             # r6: the HBM traffic of the dominant launch measured by this very run (two child processes under rocprofv3 --pmc), per launch like `achieved`
             live = pmc_traffic(args, "mfma_filter_kernel_v7", krows)
             roof["traffic_measurement"] = live
@@ -702,7 +741,7 @@ def main():
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": ("weak" if world > 1 else None),
             "vs_baseline": None,
             "value_device_resident": qps,   # (= value: queries generated on the device, results left there - the contract's timed region)
-            "end_to_end": e2e,              # the same steps host -> host, copies overlapped; None with --no-e2e
+            "end_to_end": e2e,              # the same steps host -> host, copies overlapped; None without --full or with --no-e2e
             "dtype": ("f32 (exact fp32 distances; the batched scan runs %s as a lower-bound filter, survivors re-ranked in fp32)"
                       % ("an int8 MFMA pass (int32 accumulation) over an 8-bit mirror of the rows" if int(st.get("main_kernel_bits", 0)) == 8 else
                          "an fp16 MFMA pass (fp32 accumulation) over a half mirror of the rows" if int(st.get("main_kernel_bits", 0)) == 16 else "no matrix pass"))
@@ -711,7 +750,7 @@ def main():
                                                                 else "synthetic (manifold: 16-dimensional uniform latent embedded in %d dimensions + 1%% noise - tertiary set, not the BASELINE recipe)" % d),
             "recall_at_10": recall,
             "recall_check": {"queries": nrec, "ground_truth": "exact fp32 direct-form stream scan of all rows (EPS_FLAT_STREAM)",
-                             "ground_truth_vs_torch_fp32_scan": gt_vs_torch, "torch_queries": ntorch},
+                             "ground_truth_vs_torch_fp32_scan": gt_vs_torch, "torch_queries": ntorch} if recall is not None else None,
             "config": {"workload": "%dM x %d L2 %s, k=%d, batch=%d per step, %d rows per GPU, %d GPU(s), rows_total=%d%s"
                                    % ((n * world) // 1_000_000, d, "exact flat scan" if args.mode == "flat" else "graph traversal T=%d L=%d" % (args.T, args.L),
                                       k, b, n, world, n * world,
@@ -740,7 +779,7 @@ def main():
         if secondary:
             res["secondary_traversal"] = secondary
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             try:
                 cpu = CpuBaseline(torch, X)
                 res["cpu_baseline"] = cpu_baseline(cpu, args, X, qlast, gt, graph_for_cpu, args.cpu_seconds,
@@ -750,7 +789,7 @@ def main():
                 res["cpu_baseline"] = {"value": None, "unit": "queries/s", "cores": os.cpu_count(), "kind": "reference",
                                        "sample": "failed: %r" % (e,)}
         # ---- the other single-GPU configurations of BASELINE.json, each with the reference's CPU path beside it
-        want = [] if (args.configs == "none" or world > 1 or args.mode != "flat" or args.data != "uniform") else args.configs.split(",")
+        want = [] if (not args.full or args.configs == "none" or world > 1 or args.mode != "flat" or args.data != "uniform") else args.configs.split(",")
         if want:
             res["configs"] = {}
             if "c2" in want and args.graph_rows and args.graph_rows <= n:

@@ -509,12 +509,12 @@ def config_c1(args):
     """BASELINE configs[0]: 100k x 128 VECTOR_FLOAT EUCLIDEAN through engine/bindings - the `epsilla` CPython module
     (bindings/python/interface.cpp:260-331, unmodified in both builds): insert() in 1000-row JSON batches, 1000 query() calls, k = 10.
     Two modules, each in a process of its own (scripts/epsilla_module_driver.py): the reference's own build (oracle/_ref/pymod: the CPU
-    engine) and the drop-in build (dropin/_build: the same binding over libepsilla_gfx950).  The binding never rebuilds, so both answer
+    engine) and the drop-in build (oracle/_ref/dropin: the same binding over libepsilla_gfx950).  The binding never rebuilds, so both answer
     with the exact scan; the answers are compared id by id."""
     import subprocess
     import tempfile
     drv = os.path.join(ROOT, "scripts", "epsilla_module_driver.py")
-    mods = (("reference_cpu", os.path.join(ROOT, "oracle", "_ref", "pymod")), ("gfx950_dropin", os.path.join(ROOT, "dropin", "_build")))
+    mods = (("reference_cpu", os.path.join(ROOT, "oracle", "_ref", "pymod")), ("gfx950_dropin", os.path.join(ROOT, "oracle", "_ref", "dropin")))
     out = {"workload": "100k x 128 EUCLIDEAN through the `epsilla` CPython module: insert() in 1000-row JSON batches, 1000 sequential query() calls (one host vector in, "
                        "a list of dicts out), k=10; per call everything included (JSON, GIL, H2D / D2H on the GPU side)"}
     answers = {}

@@ -21,7 +21,8 @@ except ImportError:
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libepsilla_oracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libepsilla_ref.so")
-DROPIN_SO = os.path.join(os.path.dirname(HERE), "dropin", "_build", "libepsilla_dropin.so")
+DROPIN_DIR = os.path.join(HERE, "_ref", "dropin")   # (built from the reference's sources: lives with them under _ref)
+DROPIN_SO = os.path.join(DROPIN_DIR, "libepsilla_dropin.so")
 
 i64 = C.c_int64
 fptr = C.POINTER(C.c_float)
@@ -280,14 +281,14 @@ def dropin_available():
 
 
 def build_dropin():
-    subprocess.check_call(["make", "-s", "-C", os.path.dirname(DROPIN_SO).rsplit("/_build", 1)[0], "-j8"])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(os.path.dirname(HERE), "dropin"), "OUT=" + DROPIN_DIR, "-j8"])
 
 
 class Ref:
     """The reference itself (compiled verbatim). See oracle/ref_driver.cpp."""
 
     def __init__(self, path=REF_SO):
-        """path may also be dropin/_build/libepsilla_dropin.so (the reference's DBMS layers over the gfx950
+        """path may also be oracle/_ref/dropin/libepsilla_dropin.so (the reference's DBMS layers over the gfx950
         executor): that build exports only the DBServer-level entry points, so missing low-level symbols are skipped."""
         real = C.CDLL(path)
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Drives an `epsilla` CPython module (the reference's own build under oracle/_ref/pymod, or the gfx950 drop-in build under
-dropin/_build) through the reference's binding API and prints one JSON document.  Run in a fresh process with the
+oracle/_ref/dropin) through the reference's binding API and prints one JSON document.  Run in a fresh process with the
 module directory first on sys.path:
     python scripts/epsilla_module_driver.py MODULE_DIR DB_PATH cities|batch|c1 [rows] [dim] [queries]
   cities  the fixture of engine/test/bindings/python/test.py (5 cities, 3 metrics, filter, duplicate PK, delete)

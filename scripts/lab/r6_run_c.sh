@@ -8,8 +8,8 @@ mkdir -p $O
 cd $R
 (timeout 1500 python -m pytest tests/test_gpu_rotated_frame.py tests/test_gpu_mfma_i8.py tests/test_gpu_full_size.py -m gpu -q -x --timeout 1400 2>&1 | tail -15 > $O/tests.txt)
 (timeout 600 python scripts/lab/r6_embedding_steps.py 10000000 10 2>&1 | grep "embedding-like" > $O/embedding_steps.txt)
-(timeout 900 python bench.py --configs embedding --cpu-seconds 0 --graph-rows 0 > $O/bench_embedding_only.json 2> $O/bench_embedding_only.err)
-(timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err)
+(timeout 900 python bench.py --full --configs embedding --cpu-seconds 0 --graph-rows 0 > $O/bench_embedding_only.json 2> $O/bench_embedding_only.err)
+(timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err)
 tail -4 $O/tests.txt; cat $O/embedding_steps.txt
 python - <<'PY'
 import json

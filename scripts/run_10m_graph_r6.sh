@@ -21,6 +21,6 @@ f=$(find $O/prof_graph_stats -name "*.db" | head -1); [ -n "$f" ] && python scri
 f1=$(find $O/prof_graph_fetch -name "*.db" | head -1); f2=$(find $O/prof_graph_write -name "*.db" | head -1)
 [ -n "$f1" ] && python scripts/rocpd_pmc.py $O/graph_10M_pmc.csv $f1 $f2 | grep -E "kernel,|eps" | head -40
 # (the contract line LAST: its traffic_reference then names the PMC file this very run leaves - VERDICT r5 9c)
-(timeout 900 python bench.py --mode graph --load-graph /tmp/g10m.bin --T 4 --L 500 --steps 5 --warmup 2 --cpu-seconds 40 --configs none > $O/bench_graph_10M.json 2> $O/bench_graph_10M.err)
+(timeout 900 python bench.py --full --mode graph --load-graph /tmp/g10m.bin --T 4 --L 500 --steps 5 --warmup 2 --cpu-seconds 40 --configs none > $O/bench_graph_10M.json 2> $O/bench_graph_10M.err)
 find $O -name "*.db" -size +20M -delete
 du -sh $O

@@ -20,6 +20,6 @@ f=$(find $O/prof_stats -name "*.db" | head -1); [ -n "$f" ] && python scripts/ro
 f1=$(find $O/prof_fetch -name "*.db" | head -1); f2=$(find $O/prof_write -name "*.db" | head -1); f3=$(find $O/prof_sq -name "*.db" | head -1)
 [ -n "$f1" ] && python scripts/rocpd_pmc.py $O/pmc.csv $f1 $f2 $f3 | grep -E "kernel,|mfma_filter|rerank" | head -40
 cd $R
-(timeout 900 python bench.py --steps $STEPS --warmup 5 > $O/bench.json 2> $O/bench.err)
+(timeout 900 python bench.py --full --steps $STEPS --warmup 5 > $O/bench.json 2> $O/bench.err)
 find $O -name "*.db" -size +20M -delete
 du -sh $O

@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 (timeout 1800 python -m pytest tests -m gpu -q --timeout 1500 2>&1 | tail -12 > $O/gpu_tests.txt)
 unset EPS_TUNING_FROM_ENV
-(timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err)
+(timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err)
 export EPS_TUNING_FROM_ENV=1
 (EPS_DEBUG=1 timeout 1500 python scripts/bench_graph.py --rows 10000000 --dim 768 --data uniform --L 500,1000,2000 --T 1,4 --reps 2 > $O/graph_10M_uniform.jsonl 2> $O/graph_10M_uniform.err)
 grep "eps build" $O/graph_10M_uniform.err > $O/graph_10M_build.txt

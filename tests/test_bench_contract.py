@@ -1,4 +1,4 @@
-"""bench.py's output contract (one JSON line with the driver's keys, `roofline` and `cpu_baseline`), on a small workload."""
+"""bench.py's output contract (one JSON line with the driver's keys, `roofline` and - under --full - `cpu_baseline`), on a small workload."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--rows", "300000",
-                        "--batch", "256", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--batch", "256", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -54,7 +54,7 @@ def test_bench_two_ranks_on_one_gpu_merge_equals_unsharded_scan():
     env = dict(os.environ, EPS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--rows", "150000", "--batch", "96", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--rows", "150000", "--batch", "96", "--cpu-seconds", "0", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -75,7 +75,7 @@ def test_bench_eight_ranks_on_one_gpu():
     env = dict(os.environ, EPS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--rows", "80000", "--batch", "160", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
+                        "--rows", "80000", "--batch", "160", "--cpu-seconds", "0", "--full"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -103,6 +103,50 @@ def _check_exchange(d, world, batch, k):
     assert d["value_device_resident"] == d["value"]
 
 
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_step_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline step alone (contract keys, roofline of the timed launches, no leg beside it), and
+    --dump-outputs writes what the last timed step returned: seeded inputs, so two runs with the same arguments dump the same answers,
+    and those are the exact top-k of the last query batch (checked here for 8 queries against a torch fp32 scan of the same rows)."""
+    import numpy as np
+    steps, warmup, n, d, b, k = 3, 1, 300000, 768, 256, 10
+    dumps = []
+    for i in range(2):
+        out = str(tmp_path / ("run%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--rows", str(n),
+                            "--batch", str(b), "--dump-outputs", out], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert key in line, key
+        assert line["steps"] == steps and line["warmup"] == warmup and abs(line["value"] - b * 1000.0 / line["ms_per_step"]) < 1e-6 * line["value"]
+        for key in ("cpu_baseline", "configs", "secondary_traversal"):
+            assert key not in line, key
+        assert line["end_to_end"] is None and line["recall_at_10"] is None and "under_load" not in line["roofline"]
+        got = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+        assert sorted(got) == ["counts", "distances", "ids"], sorted(got)
+        assert got["ids"].dtype == np.float64 and got["ids"].shape == (b, k) and got["distances"].dtype == np.float32 and got["distances"].shape == (b, k)
+        assert (got["counts"] == k).all() and (got["ids"] >= 0).all() and (got["ids"] < n).all() and (np.diff(got["distances"], axis=1) >= 0).all()
+        dumps.append(got)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    import torch
+    sys.path.insert(0, ROOT)
+    from bench_legs import exact_topk_torch, gen_rows
+    dev = torch.device("cuda", 0)
+    X = gen_rows(torch, n, d, 42, dev, "uniform")
+    gq = torch.Generator(device=dev).manual_seed(43)
+    q = [torch.rand((b, d), generator=gq, device=dev, dtype=torch.float32) for _ in range(steps + warmup)][-1]
+    hits = 0
+    for qi in range(8):
+        td, ti = exact_topk_torch(torch, X, q[qi], k, 0, 1)
+        hits += len(set(ti.tolist()) & set(dumps[0]["ids"][qi].astype(np.int64).tolist()))
+        assert np.allclose(dumps[0]["distances"][qi], td.cpu().numpy(), rtol=1e-4, atol=1e-4), qi
+    assert hits >= 0.99 * 8 * k, hits
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus():
     """`--gpus N` is what the line reports as n_gpus: under a launcher that started a different number of ranks bench.py stops
     instead of measuring fewer GPUs than asked for (r3's flag was parsed and never read).  CPU-only: fails before any device call."""
@@ -119,7 +163,7 @@ def test_bench_launches_its_own_ranks_when_started_plain():
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(EPS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "120000", "--batch", "64",
-                        "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--cpu-seconds", "0", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -133,7 +177,7 @@ def test_bench_inproc_shard_group():
     and results in device memory, merge on device 0) under the same JSON contract; two shards on this box's one GPU."""
     env = dict(os.environ, EPS_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--inproc", "--steps", "2", "--warmup", "1", "--rows", "120000",
-                        "--batch", "64"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--batch", "64", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

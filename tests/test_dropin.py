@@ -38,7 +38,7 @@ def dropin():
         build()
         build_dropin()
     if not dropin_available():
-        pytest.skip("dropin/_build/libepsilla_dropin.so not built (needs /root/reference; `make -C dropin`)")
+        pytest.skip("oracle/_ref/dropin/libepsilla_dropin.so not built (needs the reference's sources: `make -C dropin OUT=$PWD/oracle/_ref/dropin`)")
     return Ref(DROPIN_SO)
 
 

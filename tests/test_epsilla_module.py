@@ -1,5 +1,5 @@
 """The `epsilla` CPython module (SURVEY 8b "Python-module ABI").  oracle/_ref/pymod/epsilla.so is the reference's own binding
-over the reference engine; dropin/_build/epsilla.so is the SAME binding source (bindings/python/interface.cpp, unmodified)
+over the reference engine; oracle/_ref/dropin/epsilla.so (dropin/Makefile) is the SAME binding source (bindings/python/interface.cpp, unmodified)
 over this repository's executor + libepsilla_gfx950.so, plus the additive rebuild() / query_batch().  Each module runs in its
 own process (both are called `epsilla`)."""
 import json
@@ -13,7 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref", "pymod")
-GPU_DIR = os.path.join(ROOT, "dropin", "_build")
+GPU_DIR = os.path.join(ROOT, "oracle", "_ref", "dropin")
 DRIVER = os.path.join(ROOT, "scripts", "epsilla_module_driver.py")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "epsilla_module_cities.json")
 
@@ -61,7 +61,7 @@ def test_gfx950_module_answers_like_the_reference_module():
     """same binding source over the MI355X executor: identical rows / order / distances for every metric and filter of the
     fixture (golden = the reference module's answers), incl. string and OR / NOT filters and the delete."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     out = _run(GPU_DIR, "cities")
     assert out["module"] == "gfx950"
     gold = json.load(open(GOLDEN))
@@ -81,7 +81,7 @@ def test_gfx950_module_rebuild_and_query_batch():
     returns what N query() calls return.  3000 x 32: the flat answers equal the reference module's, the graph answers (T = 4,
     L = 500 on 3000 rows: everything is evaluated) equal the flat ones."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     out = _run(GPU_DIR, "batch", 3000, 32, 48)
     assert out["rebuild_code"] == 0 and out["query_batch"]["code"] == 0
     flat, graph, qb = out["flat"]["results"], out["graph"]["results"], out["query_batch"]["results"]
@@ -103,7 +103,7 @@ def test_gfx950_module_query_batch_is_one_device_batch_and_equals_single_queries
     is brought in through the reference's own file loader from files written in its format (100 000 rows: within the reference
     binding's own 150 000-row capacity, so its module loads the same files side by side)."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     rows, dim, nq = 100_000, 64, 300
     out = _run(GPU_DIR, "bulk", rows, dim, nq)
     for flt in ("", "ID < %d" % (rows // 2)):
@@ -133,7 +133,7 @@ def test_gfx950_module_loads_on_cpu_and_refuses_to_search_without_a_gpu():
     """CPU: the drop-in module imports (the reference binding's 8 methods + rebuild + query_batch), ingests through the unchanged
     DBServer, and a query fails loudly when no gfx950 device is usable - there is no CPU fallback behind the binding either."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     import torch
     code = r'''
 import sys, ctypes
@@ -173,7 +173,7 @@ def test_gfx950_module_insert_array_leaves_the_table_the_json_insert_leaves():
     different batch boundaries on the two sides, deletes afterwards.  Every query() / query_batch() answer - ids, distances, attributes,
     the stored vectors themselves - is identical; capacity and missing-field errors read like the reference's; upsert replaces a row."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     rows = 100_000
     out = _run(GPU_DIR, "ingest", rows, 48, 40)
     assert out["json_codes_ok"] and out["delete_codes"] == [0, 0]
@@ -203,7 +203,7 @@ def test_gfx950_module_insert_array_argument_checks_on_cpu():
     are C-contiguous buffers, STRING columns lists of str, all of one length; n = 0 is a no-op; float64 vectors and VECTOR_DOUBLE fields are stored as the
     JSON path stores them (rounded to float32); a primary key repeated inside the call is skipped as `insert` skips it."""
     if not _have(GPU_DIR):
-        pytest.skip("dropin/_build/epsilla.so not built (make -C dropin)")
+        pytest.skip("oracle/_ref/dropin/epsilla.so not built (make -C dropin OUT=$PWD/oracle/_ref/dropin)")
     code = r'''
 import sys, ctypes
 import numpy as np

@@ -152,7 +152,7 @@ def test_dropin_dbserver_over_a_sharded_executor(tmp_path):
     flat answers, device-compiled and host-evaluated filters, deletes; equal to the reference DBServer's own (exact at this size)."""
     from oracle.pyoracle import DROPIN_SO, Ref, dropin_available, ref_available
     if not (dropin_available() and ref_available()):
-        pytest.skip("needs dropin/_build and oracle/_ref")
+        pytest.skip("needs oracle/_ref/dropin and oracle/_ref")
     os.environ["EPS_DEVICES"] = "0,0"
     try:
         ref, drop = Ref(), Ref(DROPIN_SO)
@@ -193,7 +193,7 @@ def test_dropin_rebuild_builds_per_shard_graphs_on_the_mirror(tmp_path):
     rebuild are found through the shards' brute-force tails."""
     from oracle.pyoracle import DROPIN_SO, Ref, dropin_available, ref_available
     if not (dropin_available() and ref_available()):
-        pytest.skip("needs dropin/_build and oracle/_ref")
+        pytest.skip("needs oracle/_ref/dropin and oracle/_ref")
     os.environ["EPS_DEVICES"] = "0,0"
     try:
         ref, drop = Ref(), Ref(DROPIN_SO)
