@@ -368,17 +368,17 @@ void eps_exchange_destroy(eps_exchange* x);
 /* Engine-selection switches.  The library reads NO environment variable: what used to be lab switches are entries of one
  * process-wide table that only this call writes (name, value as text; value == NULL removes the entry; name == NULL empties
  * the table).  No entry changes a result - they pick between engines that return the same bits (tests/ run every answer
- * through both sides of each) or turn diagnostics on:
- *   EPS_DEBUG (stage log on stderr), EPS_TRV_PROF (traversal phase profile on stderr),
+ * through both sides of each) or turn diagnostics on.  A name not listed here is stored and ignored:
+ *   EPS_DEBUG (stage log on stderr), EPS_DEBUG_ONE_PASS_OVERFLOW (the one-pass search's log on stderr after a call that overflowed),
+ *   EPS_TRV_PROF (traversal phase profile on stderr),
  *   EPS_TRV_PREFILTER 0|1 (8-bit lower-bound test of the traversal), EPS_TRV_VISITED bitmap|stamps, EPS_TRV_STAMP_START, EPS_TRV_WAVES 4|8|16, EPS_TRV_PER_CU, EPS_TRV_LDS_KB,
- *   EPS_FLAT_ONE_PASS 0|1, EPS_ONE_PASS_TIMED, EPS_S8_WG_PER_CU, EPS_S8_HOST_WORDS 0|1, EPS_S8_TWO_LAUNCHES 0|1, EPS_S8_MAX_Q 1..16, EPS_S8_MAX_K 1..64, EPS_S8_FILTER_PROGRAMS 0|1, EPS_S8_RERANK 0|1, EPS_HOST_STAGING 0|1, EPS_RERANK_SPLIT, EPS_MFMA_BITS 8|16, EPS_MFMA_MAX_BATCH,
- *   EPS_MFMA_PROBE, EPS_MFMA_SEED, EPS_MFMA_GROUPSYNC, EPS_MFMA_SYNC_SHIFT, EPS_MFMA_STAGES, EPS_MFMA_KERNEL, EPS_MFMA_NARROW,
- *   EPS_MFMA_TWO_PER_CU, EPS_MFMA_FOLD, EPS_MFMA_MANTISSA, EPS_BUILD_BLOCK, EPS_BUILD_VISITED, EPS_BUILD_PREFILTER,
+ *   EPS_FLAT_ONE_PASS 0|1, EPS_ONE_PASS_TIMED, EPS_S8_WG_PER_CU, EPS_S8_HOST_WORDS 0|1, EPS_S8_TWO_LAUNCHES 0|1, EPS_S8_MAX_Q 1..32, EPS_S8_MAX_K 1..64, EPS_S8_FILTER_PROGRAMS 0|1, EPS_S8_RERANK 0|1, EPS_HOST_STAGING 0|1, EPS_RERANK_SPLIT, EPS_MFMA_BITS 8|16, EPS_MFMA_MAX_BATCH,
+ *   EPS_MFMA_PROBE, EPS_MFMA_SEED, EPS_MFMA_GROUPSYNC, EPS_MFMA_SYNC_SHIFT, EPS_MFMA_STAGES, EPS_MFMA_NARROW,
+ *   EPS_MFMA_FOLD, EPS_MFMA_MANTISSA, EPS_BUILD_BLOCK, EPS_BUILD_VISITED, EPS_BUILD_PREFILTER,
  *   EPS_MIRROR_ROTATE 0|1 (frame of the 8-bit grid: identity | rotated; unset = chosen per table when its mirror is first built; read at that moment only),
  *   EPS_MIRROR_CLIP e (the grid cuts 10^-e of the sampled values off each tail, 1 <= e <= 9, in either frame; unset = 10^-7, rotated frame 10^-6;
  *   read when the mirror is first built), EPS_S8_FOLD 0|1 (the one-pass search on tables whose margins are folded per batch).
- * Switches that make answers WRONG on purpose (kernel ablations for profiling) exist only in a lab build (-DEPS_LAB), which
- * also falls back to the environment for names the table does not hold.  Returns EPS_OK. */
+ * Returns EPS_OK. */
 int32_t eps_set_tuning(const char* name, const char* value);
 
 #ifdef __cplusplus

@@ -183,7 +183,7 @@ def c2b():
         el = (time.perf_counter() - t1) / 3
         st = ix.stats()
         byt = st["dist_evals"] * (4 * d + 4) + st["expansions"] * (4 * 52)
-        print(json.dumps({"config": "C2b 1M x 768 graph traversal batch=1024 T=%d L=%d wide=%s" % (T, L, os.environ.get("EPS_TRV_WIDE", "auto")),
+        print(json.dumps({"config": "C2b 1M x 768 graph traversal batch=1024 T=%d L=%d waves=%s" % (T, L, os.environ.get("EPS_TRV_WAVES", "auto")),
                           "qps": b / el, "recall_at_10": recall(ob[0].cpu().numpy(), gti), "evals_per_query": st["dist_evals"] / float(b),
                           "kernel_ms": st["main_kernel_ms"], "achieved_GBps": byt / (st["main_kernel_ms"] * 1e-3) / 1e9,
                           "frac_of_8TBps": byt / (st["main_kernel_ms"] * 1e-3) / 8e12}))

@@ -133,10 +133,10 @@ def test_traversal_gather_bytes_accounting():
     assert amd.traversal_gather_bytes(dict(off, rerank_rows=1), 100, deg, 0) > 0     # d not a multiple of 16: mirror row rounded up to 112
 
 
-def test_product_library_reads_no_environment_and_ships_no_ablation(built):
+def test_product_library_reads_no_environment_and_has_no_lab_build(built):
     """a production library must not change its behaviour - let alone its answers - because of an environment variable.
-    The product .so imports no getenv at all (its engine switches are entries of the eps_set_tuning table), and the kernel-ablation
-    switches, which make answers wrong on purpose, exist in lab builds (-DEPS_LAB) only."""
+    The product .so imports no getenv at all (its engine switches are entries of the eps_set_tuning table), and the sources hold no
+    lab build mode and no kernel ablation (switches that make answers wrong on purpose) in any build."""
     import subprocess
     undefined = subprocess.run(["nm", "-D", "--undefined-only", built], capture_output=True, text=True).stdout
     assert not re.search(r"\b(secure_)?getenv\b", undefined), [ln for ln in undefined.splitlines() if "getenv" in ln]
@@ -146,8 +146,24 @@ def test_product_library_reads_no_environment_and_ships_no_ablation(built):
     src = ""
     for f in os.listdir(os.path.join(ROOT, "vectordb_amd", "csrc")):
         src += open(os.path.join(ROOT, "vectordb_amd", "csrc", f), errors="ignore").read()
-    # the only getenv left in the sources is the lab build's fallback inside tune_env
-    assert len(re.findall(r"\bgetenv\(", src)) == 1 and "#ifdef EPS_LAB\n  return getenv(name);" in src
+    for s in ("getenv(", "EPS_LAB", "EPS_V7_", "ABLATE"):
+        assert s not in src, s
+
+
+def test_tuning_names_agree():
+    """One list of switches: the names the library's sources look up (tune_int / tune_env), the names the Python wrapper forwards
+    (TUNING_NAMES) and the names the eps_set_tuning comment of the public header documents are the same set."""
+    from vectordb_amd import _lib
+    csrc = os.path.join(ROOT, "vectordb_amd", "csrc")
+    used = set()
+    for f in os.listdir(csrc):
+        used |= set(re.findall(r"\btune_(?:int|env)\(\s*\"(EPS_[A-Z0-9_]+)\"", open(os.path.join(csrc, f), errors="ignore").read()))
+    hdr = open(os.path.join(ROOT, "include", "epsilla_gfx950.h")).read()
+    head = hdr[:hdr.index("int32_t eps_set_tuning(")]
+    documented = set(re.findall(r"EPS_[A-Z0-9_]+", head[head.rindex("/*"):])) - {"EPS_OK"}
+    assert len(used) >= 30, sorted(used)
+    assert used == set(_lib.TUNING_NAMES), (sorted(used - set(_lib.TUNING_NAMES)), sorted(set(_lib.TUNING_NAMES) - used))
+    assert used == documented, (sorted(used - documented), sorted(documented - used))
 
 
 def test_tuning_table(built):

@@ -334,8 +334,8 @@ __host__ __device__ inline int group_lanes(int64_t dim, bool vec4) {
 // count, so hipcc issues the U loads of one piece, waits for them, multiplies, and only then issues the next piece: at d = 768
 // (three pieces per lane) a GATHER of U rows costs three dependent memory round trips.  NL = 3 issues all of them first; the
 // fmas run in the same order either way, so the sums are bit-identical.  It costs 32 more VGPRs at U = 4 and every kernel that
-// gathers rows is at its occupancy edge, so it is a lab knob, not the default (profiles/r3_row_pieces_in_flight_ab.txt): traversal
-// with the 8-bit prefilter (-DEPS_TRV_NL=3) 1M x 768: T = 1 8.85 -> 8.03 ms, T = 4 7.26 -> 6.92 ms, but 10M x 768 T = 4 10.2 ->
+// gathers rows is at its occupancy edge, so each caller picks its own NL (profiles/r3_row_pieces_in_flight_ab.txt): traversal
+// with the 8-bit prefilter (NL = 3; TRV2_NL since r5) 1M x 768: T = 1 8.85 -> 8.03 ms, T = 4 7.26 -> 6.92 ms, but 10M x 768 T = 4 10.2 ->
 // 10.4 ms (T = 1 11.3 -> 10.6); without the prefilter 13.0 -> 16.6 ms (4 -> 3 wavefronts per SIMD); the build's searches
 // (Link 2.74 -> 2.88 s); the re-rank: no change.
 template <int U, int NQ, bool VEC4, int NL = 1>

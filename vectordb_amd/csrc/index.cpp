@@ -34,11 +34,7 @@ const char* tune_env(const char* name) {
       if (it != g_tune.end()) return it->second;
     }
   }
-#ifdef EPS_LAB
-  return getenv(name);
-#else
   return nullptr;
-#endif
 }
 int tune_int(const char* name, int dflt) {
   const char* e = tune_env(name);

@@ -65,7 +65,7 @@ struct ScratchClaim {
 size_t scratch_reclaim();   // bytes released
 
 // Engine-selection switches (eps_set_tuning, include/epsilla_gfx950.h): the value of `name` in the process-wide table, or null.  The
-// product library never reads the environment; a lab build (-DEPS_LAB) falls back to getenv for names the table does not hold.
+// library never reads the environment.
 const char* tune_env(const char* name);
 // the integer value of a switch, read ONCE (a second lookup may find the entry gone: eps_set_tuning is a process-wide runtime call), or `dflt`
 int tune_int(const char* name, int dflt);

@@ -1251,11 +1251,6 @@ static int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k,
   a.dim = (int)ix.dim_;
   a.step = m.step8;
   a.inv_step = 1.f / m.step8;
-#ifdef EPS_LAB   // (kernel ablations make answers wrong on purpose: lab builds only)
-  a.ablate = tune_int("EPS_S8_ABLATE", 0);
-#else
-  a.ablate = 0;
-#endif
   if (!m.s8_cus) {   // (once per mirror: the query costs more than the search)
     hipDeviceProp_t prop;
     m.s8_cus = hipGetDeviceProperties(&prop, ix.device_) == hipSuccess ? std::max(8, prop.multiProcessorCount) : 256;
@@ -1451,10 +1446,8 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   if (!m.qstat.reserve((size_t)b_pad * 16) || !m.T.reserve((size_t)b_pad * 4) || !m.cand.reserve((size_t)nq * cap * 8) ||
       !m.cnt.reserve((size_t)(nq + 4) * 4 + 16) || !m.seedc.reserve((size_t)nq * k * 4) || !(i8 ? m.q8.reserve((size_t)b_pad * m.d_pad8) : m.qh.reserve((size_t)b_pad * m.d_pad * 2)))
     return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
-  // kernel choice: v5 / v7 want K-steps in pairs (d_pad % 128 == 0, >= 256); other shapes stay on v3
-  const char* ver_s = tune_env("EPS_MFMA_KERNEL");   // 3 | 7 (A/B); v7 needs K-steps in pairs, other shapes stay on v3
-  const int version_env = (ver_s && atoi(ver_s) == 3 && !i8) ? 3 : 7;
-  const int version = (version_env == 7 && (d_pad_h % 128 != 0 || d_pad_h < 256)) ? 3 : version_env;   // (the 8-bit mirror is padded for v7)
+  // kernel choice: v7 wants K-steps in pairs (d_pad % 128 == 0, >= 256); other shapes stay on v3 (the 8-bit mirror is padded for v7)
+  const int version = (d_pad_h % 128 != 0 || d_pad_h < 256) ? 3 : 7;
   if (version >= 7 && !m.qf.reserve((size_t)b_pad * d_pad_h * 2)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
   if (!m.gsync.reserve(1024)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
   // (what the staging below decides, needed here already: the 8-bit query preparation also lays down a seeded call's start state)
@@ -1586,15 +1579,6 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   fa.group_sync = nullptr;
   fa.sync_shift = std::min(8, std::max(0, tune_int("EPS_MFMA_SYNC_SHIFT", 2)));
   fa.dense = 0;
-  fa.ablate = 0;
-  fa.prof = nullptr;
-#ifdef EPS_V7_PROF
-  static DevBuf prof_buf;   // (lab builds only)
-  if (prof_buf.reserve(64)) {
-    (void)hipMemsetAsync(prof_buf.p, 0, 64, s);
-    fa.prof = prof_buf.as<unsigned long long>();
-  }
-#endif
 
   RerankArgs ra;
   ra.rows = ix.d_rows_;
@@ -1649,12 +1633,9 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
                            reinterpret_cast<const void*>(mfma_filter_kernel_v7<2, FM_DENSE, true>), reinterpret_cast<const void*>(mfma_filter_kernel_v7<1, FM_IDS, true>),
                            reinterpret_cast<const void*>(mfma_filter_kernel_v7<1, FM_KEYS, true>), reinterpret_cast<const void*>(mfma_filter_kernel_v7<1, FM_DENSE, true>)})
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V7_LDS_BYTES);
-    for (const void* fn : {reinterpret_cast<const void*>(mfma_filter_kernel_v7<2, FM_IDS, true, 4>), reinterpret_cast<const void*>(mfma_filter_kernel_v7<2, FM_KEYS, true, 4>)})
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v7_lds_bytes(4));
   }
   const int num_cus = m.num_cus;
   const bool narrow_env = !(tune_int("EPS_MFMA_NARROW", 1) == 0);
-  const bool two_per_cu = tune_int("EPS_MFMA_TWO_PER_CU", 0) != 0;   // (lab until measured)
   auto launch_filter = [&](const FilterArgs& f) {
     {
       FilterArgs f3 = f;
@@ -1664,7 +1645,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
         if (f3.group_sync && f3.dense && !prologue) (void)hipMemsetAsync(f3.group_sync, 0, 1024, s);   // (stages: reset by threshold_kernel / the re-rank)
         const int mode = f3.dense ? FM_DENSE : (f3.cand_keys ? FM_KEYS : FM_IDS);
         const dim3 grid((unsigned)num_cus), block(256);
-#define EPS_V7_LAUNCH(JQ_, I8_)                                                                                             \
+#define EPS_LAUNCH_V7(JQ_, I8_)                                                                                             \
   do {                                                                                                                      \
     if (mode == FM_DENSE) hipLaunchKernelGGL((mfma_filter_kernel_v7<JQ_, FM_DENSE, I8_>), grid, block, shm, s, f3);         \
     else if (mode == FM_KEYS) hipLaunchKernelGGL((mfma_filter_kernel_v7<JQ_, FM_KEYS, I8_>), grid, block, shm, s, f3);      \
@@ -1672,18 +1653,11 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   } while (0)
         if (nq <= 128 && narrow_env) {   // one 128-query tile: half the padded MFMA work, the pass streams the mirror
           f3.tiles_q = 1;
-          if (i8) EPS_V7_LAUNCH(1, true); else EPS_V7_LAUNCH(1, false);
-        } else if (i8 && mode != FM_DENSE && two_per_cu) {
-          // r4: 128-row tiles, two workgroups per CU (see the kernel: NRB = 4)
-          f3.tile0 *= 2;
-          f3.ntiles *= 2;
-          const dim3 grid2((unsigned)num_cus * 2);
-          if (mode == FM_KEYS) hipLaunchKernelGGL((mfma_filter_kernel_v7<2, FM_KEYS, true, 4>), grid2, block, v7_lds_bytes(4), s, f3);
-          else hipLaunchKernelGGL((mfma_filter_kernel_v7<2, FM_IDS, true, 4>), grid2, block, v7_lds_bytes(4), s, f3);
+          if (i8) EPS_LAUNCH_V7(1, true); else EPS_LAUNCH_V7(1, false);
         } else {
-          if (i8) EPS_V7_LAUNCH(2, true); else EPS_V7_LAUNCH(2, false);
+          if (i8) EPS_LAUNCH_V7(2, true); else EPS_LAUNCH_V7(2, false);
         }
-#undef EPS_V7_LAUNCH
+#undef EPS_LAUNCH_V7
       }
       else hipLaunchKernelGGL(mfma_filter_kernel_v3, dim3((unsigned)num_cus), dim3(512), shm, s, f3);
     }
@@ -1869,21 +1843,13 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   if (er == hipSuccess) er = hipMemcpyAsync(&h.total, total, 8, hipMemcpyDeviceToHost, s);
   if (er == hipSuccess) er = hipStreamSynchronize(s);
   if (er != hipSuccess) return ix.hip_fail(er, "MFMA filter");
-#ifdef EPS_V7_PROF
-  if (fa.prof) {
-    unsigned long long pr[4] = {0, 0, 0, 0};
-    (void)hipMemcpy(pr, fa.prof, 32, hipMemcpyDeviceToHost);
-    if (pr[3]) fprintf(stderr, "[eps v7 prof] wave-tiles %llu: head %.0f  K loop %.0f  epilogue %.0f cycles per tile (all stages of this call)\n", pr[3],
-                       (double)pr[0] / pr[3], (double)pr[1] / pr[3], (double)pr[2] / pr[3]);
-  }
-#endif
   ix.stats_.rerank_rows += (int64_t)h.total;
   ix.stats_.dist_evals += nq * (n - bounds[0]) + (seeded ? nq * S0 : 0);   // (exact mode visits the head twice)
   ix.stats_.main_kernel_launches = 1;
   if (h.overflow) {
     ix.result_finalized_ = false;   // (whatever was converted before the sync is stale: a pass below rewrites the result keys)
     ix.stats_.overflow_queries += h.overflow;
-    if (!approx && !fa.ablate) {
+    if (!approx) {
       // (selective filters inflate the lists by 1 / pass fraction, adversarial row orders by more): first retry with 16 x
       // the candidate slots - re-ranking tens of thousands of rows per query is still ~50 x cheaper than the stream scan
       // of a large batch - then the exact stream engine

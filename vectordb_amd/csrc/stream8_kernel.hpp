@@ -37,13 +37,6 @@
 
 namespace eps {
 
-// kernel ablations (profiling; the answers are wrong) exist in lab builds only: in the product they compile away
-#ifdef EPS_LAB
-#define S8_ABLATE (a.ablate)
-#else
-#define S8_ABLATE 0
-#endif
-
 
 struct Stream8Args {
   const signed char* x8;   // [n_pad8][d_pad8]
@@ -68,9 +61,6 @@ struct Stream8Args {
   float* qstat_out = nullptr;    // = qstat, writable
   int dim = 0;
   float step = 1.f, inv_step = 1.f;
-  int ablate;              // lab (EPS_S8_ABLATE; results are wrong): 1 = no table, no test - the bare stream + dot products; 2 = no periodic
-                           // re-read of the table; 4 = no start-up (offer, barriers, first read), tests against "nothing passes"; 8 = the
-                           // start-up as it is, then tests against "nothing passes"
   FilterSpec f;
 };
 
@@ -300,15 +290,6 @@ __global__ __launch_bounds__(256, 2) void stream8_kernel(Stream8Args a) {
   for (int q = 0; q < NQ; ++q) mine[q] = 0;
   // candidates of one chunk: appended to the wavefront's own list, offered to the table where they beat its k-th slot
   auto test_chunk = [&](int64_t base, const int (&acc)[U][NQ]) __attribute__((always_inline)) {
-    if (S8_ABLATE & 1) {   // (keeps the loads and the arithmetic alive)
-      int x = 0;
-#pragma unroll
-      for (int uu = 0; uu < U; ++uu)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) x ^= acc[uu][q];
-      if (x == 0x7fffffff && base == -5) a.raw[0] = 1;
-      return;
-    }
     int T[NQ], gkth[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -360,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void stream8_kernel(Stream8Args a) {
     // the best of the wavefront's 4 U rows (per query): one offer per wavefront, of a row that beat 15 others
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      if (q >= a.nq || (S8_ABLATE & 5)) continue;
+      if (q >= a.nq) continue;
       int bv = S8_EMPTY, br = 0;
 #pragma unroll
       for (int uu = 0; uu < U; ++uu) {
@@ -379,42 +360,35 @@ __global__ __launch_bounds__(256, 2) void stream8_kernel(Stream8Args a) {
       if (lane == 0 && bv != S8_EMPTY) stream8_offer(a, q, stream8_offer_value(a, bv, first + br), (u32)(first + br));
     }
   }
-  if (!(S8_ABLATE & 5)) {
-    __syncthreads();
-    // (the offers are fire-and-forget atomics: a workgroup that gets here before k slots have been filled by anyone would test its
-    // first chunk against "everything passes"; it waits for them, a few microseconds at most - bounded, then it takes what there is)
-    if (wave == 0) {
-      const int need = stream8_startup_need(a.k, SLOTS);
-      int grace = 0;
-      for (int spin = 0; spin < 48; ++spin) {
-        int state = 2;   // 0: a query has fewer than k slots filled, 1: k but not `need`, 2: every query has what it needs
+  __syncthreads();
+  // (the offers are fire-and-forget atomics: a workgroup that gets here before k slots have been filled by anyone would test its
+  // first chunk against "everything passes"; it waits for them, a few microseconds at most - bounded, then it takes what there is)
+  if (wave == 0) {
+    const int need = stream8_startup_need(a.k, SLOTS);
+    int grace = 0;
+    for (int spin = 0; spin < 48; ++spin) {
+      int state = 2;   // 0: a query has fewer than k slots filled, 1: k but not `need`, 2: every query has what it needs
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          if (q < a.nq) {
-            int gm, filled;
-            float qs[4];
+      for (int q = 0; q < NQ; ++q) {
+        if (q < a.nq) {
+          int gm, filled;
+          float qs[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) qs[i] = PREP ? qstat_s[q * 4 + i] : a.qstat[q * 4 + i];
-            const int Tq = stream8_threshold_of(a.G + q * SLOTS * S8_SLOT_STRIDE, a.k, qs, a.scal, a.metric, a.u, a.slack, lane, gm, SLOTS, &filled);
-            if (lane == 0) {
-              T_s[q] = Tq;
-              gkth_s[q] = gm;
-            }
-            const int sq = gm == S8_EMPTY ? 0 : (filled >= need ? 2 : 1);
-            state = sq < state ? sq : state;
+          for (int i = 0; i < 4; ++i) qs[i] = PREP ? qstat_s[q * 4 + i] : a.qstat[q * 4 + i];
+          const int Tq = stream8_threshold_of(a.G + q * SLOTS * S8_SLOT_STRIDE, a.k, qs, a.scal, a.metric, a.u, a.slack, lane, gm, SLOTS, &filled);
+          if (lane == 0) {
+            T_s[q] = Tq;
+            gkth_s[q] = gm;
           }
+          const int sq = gm == S8_EMPTY ? 0 : (filled >= need ? 2 : 1);
+          state = sq < state ? sq : state;
         }
-        if (state == 2 || (state == 1 && ++grace > S8_STARTUP_GRACE)) break;
-        __builtin_amdgcn_s_sleep(16);
       }
+      if (state == 2 || (state == 1 && ++grace > S8_STARTUP_GRACE)) break;
+      __builtin_amdgcn_s_sleep(16);
     }
-    __syncthreads();
   }
-  if (S8_ABLATE & 12) {
-    __syncthreads();
-    if (threadIdx.x < 4) T_s[threadIdx.x] = gkth_s[threadIdx.x] = 2147483647;
-    __syncthreads();
-  }
+  __syncthreads();
   if (first < a.n) test_chunk(first, acc);
   // ---- the stream, two chunks in flight per wavefront: the loads of chunk i + 2 are issued before chunk i + 1 is multiplied
   int it = 1;
@@ -422,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void stream8_kernel(Stream8Args a) {
     if (base + stride < a.n) load_chunk(base + stride, xa, a0a);
     // the thresholds are read again after 2, 4, 8 chunks (the table tightens fastest at the start: a stale threshold there is what lets
     // junk into the lists) and then every 8, the four wavefronts in turn (the refresher waits for 64 cache-bypassing loads)
-    if ((it == 1 || it == 3 || (it & 7) == 7) && wave == (((it >> 1) + (it >> 3)) & 3) && !(S8_ABLATE & 15)) refresh();   // (it = 1, 3, 7, 15, 23, 31, ... -> wavefront 0, 1, 3, 0, 1, 2, ...: in turn - until r4 the steady state always picked wavefront 3)
+    if ((it == 1 || it == 3 || (it & 7) == 7) && wave == (((it >> 1) + (it >> 3)) & 3)) refresh();   // (it = 1, 3, 7, 15, 23, 31, ... -> wavefront 0, 1, 3, 0, 1, 2, ...: in turn - until r4 the steady state always picked wavefront 3)
 #pragma unroll
     for (int uu = 0; uu < U; ++uu) dots(xb[uu], a0b[uu], acc[uu]);
     test_chunk(base, acc);

@@ -82,21 +82,11 @@ struct Trv2Args {
   float u8, slack8;
 };
 
-#ifndef EPS_TRV_U
-#define EPS_TRV_U 4   // rows in flight per lane group in the distance phases
-#endif
-#ifndef EPS_TRV_UPF
-#define EPS_TRV_UPF 3  // prefilter form of the kernel: fp32 rows in flight per lane group (seeds, survivors of step d0) ...
-#endif
-#ifndef EPS_TRV_NL
-#define EPS_TRV_NL 3   // ... and 16-byte pieces of each (row_dists, device_common.hpp).  r5: 3 x 3 (4 x 1 until r4; profiles/r5_traverse_lab_10M_proxy.txt)
-#endif
-#ifndef EPS_TRV_U8
-#define EPS_TRV_U8 3   // prefilter: mirror rows in flight per lane group (2 until r4) ...
-#endif
-#ifndef EPS_TRV_NL8
-#define EPS_TRV_NL8 3  // ... and 16-byte pieces of each per lane
-#endif
+constexpr int TRV2_U = 4;     // rows in flight per lane group in the distance phases
+constexpr int TRV2_UPF = 3;   // prefilter form of the kernel: fp32 rows in flight per lane group (seeds, survivors of step d0) ...
+constexpr int TRV2_NL = 3;    // ... and 16-byte pieces of each (row_dists, device_common.hpp).  r5: 3 x 3 (4 x 1 until r4; profiles/r5_traverse_lab_10M_proxy.txt)
+constexpr int TRV2_U8 = 3;    // prefilter: mirror rows in flight per lane group (2 until r4) ...
+constexpr int TRV2_NL8 = 3;   // ... and 16-byte pieces of each per lane
 constexpr int TRV2_SB = 4096;       // keys of the LDS staging block of the QGLOBAL bitonic sort
 constexpr int TRV2_MAXT = 128;      // the reference's limit for IntraQueryThreads (config/config.hpp:29)
 // ints of scalar scratch: 16 scalars, nine [TS] per-worker arrays, [16] per-wave counts, [TS + 16] edge offsets; TS = T rounded up to 16
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
   float* qst = reinterpret_cast<float*>(smem_raw + pf_off);                // [4] |q|^2, |q|, |q - qh|, C + c
   signed char* sq8 = reinterpret_cast<signed char*>(qst + 4);               // [q8len]
   const int q8len = trv2_q8len(a.cols8 > dim ? a.cols8 : dim);
-  constexpr int U8 = EPS_TRV_U8, NL8 = EPS_TRV_NL8;
+  constexpr int U8 = TRV2_U8, NL8 = TRV2_NL8;
   int G8 = 4;
   while (G8 < 64 && G8 * 16 * NL8 < q8len) G8 <<= 1;                        // lanes per mirror row (NL8 pieces of 16 bytes each)
   const int RPW8 = 64 / G8;
@@ -201,7 +191,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
   const int RPW = 64 / G;
   const int g = lane / G;
   const int t = lane & (G - 1);
-  constexpr int U = PF ? EPS_TRV_UPF : EPS_TRV_U;
+  constexpr int U = PF ? TRV2_UPF : TRV2_U;
   const int64_t slot = blockIdx.x;
   u32* vis = a.gens ? nullptr : a.visited + slot * a.words;
   u32* vlog = a.gens ? nullptr : a.vlog + slot * (int64_t)a.vcap;
@@ -253,7 +243,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
         rp[u] = a.rows + (int64_t)id[u] * dim;
       }
       float acc[U][1];
-      row_dists<U, 1, VEC4, (PF ? EPS_TRV_NL : 1)>(rp, sq, qstride, dim, a.metric, G, acc);
+      row_dists<U, 1, VEC4, (PF ? TRV2_NL : 1)>(rp, sq, qstride, dim, a.metric, G, acc);
 #pragma unroll
       for (int u = 0; u < U; ++u)
         if (ok[u] && t == 0) {
@@ -610,7 +600,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
             rp[u] = a.rows + (int64_t)id[u] * dim;
           }
           float acc[U][1];
-          row_dists<U, 1, VEC4, (PF ? EPS_TRV_NL : 1)>(rp, sq, qstride, dim, a.metric, G, acc);
+          row_dists<U, 1, VEC4, (PF ? TRV2_NL : 1)>(rp, sq, qstride, dim, a.metric, G, acc);
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             if (ok[u] && t == 0) {
