@@ -166,7 +166,7 @@ typedef struct eps_search_stats {
   int64_t filter_rows_all;  /* rows those launches covered, summed (x main_kernel_queries = the call's matrix work)              */
   int64_t i8_folded;        /* 1: the 8-bit pass of this call ran with per-row margins folded into the rows' start values (a table whose rows differ: clamped / forced outlier rows; r4) */
   int64_t i8_declined;      /* 1: this call probed the 8-bit pass on this table, found its bound too loose for the data and ran the fp16 pass (r4) */
-  int64_t one_pass;         /* 1: a handful of queries (<= 16, k <= 64; a deleted bitset, an int-column test or a compiled filter program) answered by ONE streaming pass over the 8-bit mirror + one re-rank (stream8_kernel.hpp) instead of the staged filter chain (r4) */
+  int64_t one_pass;         /* 1: a handful of queries (<= 32, k <= 64; a deleted bitset, an int-column test or a compiled filter program) answered by ONE streaming pass over the 8-bit mirror + one re-rank (stream8_kernel.hpp) instead of the staged filter chain (r4) */
   int64_t i8_rotated;       /* 1: the 8-bit pass of this call ran in the table's ROTATED frame: rows and queries quantised as R x, R a fixed orthogonal map (signs, a permutation, 256-point Walsh-Hadamard blocks) - distances do not change, the grid's step and with it the bound's margin shrink on tables whose energy sits in a few columns (unit-norm embedding rows); chosen per table when its mirror is built (r6) */
 } eps_search_stats;
 
@@ -371,13 +371,12 @@ void eps_exchange_destroy(eps_exchange* x);
  * through both sides of each) or turn diagnostics on.  A name not listed here is stored and ignored:
  *   EPS_DEBUG (stage log on stderr), EPS_DEBUG_ONE_PASS_OVERFLOW (the one-pass search's log on stderr after a call that overflowed),
  *   EPS_TRV_PROF (traversal phase profile on stderr),
- *   EPS_TRV_PREFILTER 0|1 (8-bit lower-bound test of the traversal), EPS_TRV_VISITED bitmap|stamps, EPS_TRV_STAMP_START, EPS_TRV_WAVES 4|8|16, EPS_TRV_PER_CU, EPS_TRV_LDS_KB,
- *   EPS_FLAT_ONE_PASS 0|1, EPS_ONE_PASS_TIMED, EPS_S8_WG_PER_CU, EPS_S8_HOST_WORDS 0|1, EPS_S8_TWO_LAUNCHES 0|1, EPS_S8_MAX_Q 1..32, EPS_S8_MAX_K 1..64, EPS_S8_FILTER_PROGRAMS 0|1, EPS_S8_RERANK 0|1, EPS_HOST_STAGING 0|1, EPS_RERANK_SPLIT, EPS_MFMA_BITS 8|16, EPS_MFMA_MAX_BATCH,
- *   EPS_MFMA_PROBE, EPS_MFMA_SEED, EPS_MFMA_GROUPSYNC, EPS_MFMA_SYNC_SHIFT, EPS_MFMA_STAGES, EPS_MFMA_NARROW,
- *   EPS_MFMA_FOLD, EPS_MFMA_MANTISSA, EPS_BUILD_BLOCK, EPS_BUILD_VISITED, EPS_BUILD_PREFILTER,
+ *   EPS_TRV_PREFILTER 0|1 (8-bit lower-bound test of the traversal), EPS_TRV_VISITED bitmap|stamps, EPS_TRV_STAMP_START, EPS_TRV_WAVES 4|8|16,
+ *   EPS_FLAT_ONE_PASS 0|1, EPS_ONE_PASS_TIMED, EPS_S8_HOST_WORDS 0|1, EPS_S8_TWO_LAUNCHES 0|1, EPS_S8_MAX_K 1..64, EPS_S8_FILTER_PROGRAMS 0|1, EPS_S8_RERANK 0|1,
+ *   EPS_HOST_STAGING 0|1, EPS_MFMA_MAX_BATCH, EPS_MFMA_PROBE, EPS_MFMA_SEED, EPS_MFMA_GROUPSYNC, EPS_MFMA_SYNC_SHIFT, EPS_BUILD_VISITED, EPS_BUILD_PREFILTER,
  *   EPS_MIRROR_ROTATE 0|1 (frame of the 8-bit grid: identity | rotated; unset = chosen per table when its mirror is first built; read at that moment only),
  *   EPS_MIRROR_CLIP e (the grid cuts 10^-e of the sampled values off each tail, 1 <= e <= 9, in either frame; unset = 10^-7, rotated frame 10^-6;
- *   read when the mirror is first built), EPS_S8_FOLD 0|1 (the one-pass search on tables whose margins are folded per batch).
+ *   read when the mirror is first built).
  * Returns EPS_OK. */
 int32_t eps_set_tuning(const char* name, const char* value);
 

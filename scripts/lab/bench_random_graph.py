@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Gather-bandwidth proxy for the traversal kernel at full table size WITHOUT the minutes-long graph build: a random regular
 graph (every node points at `deg` uniformly random rows) gives the kernel the same access pattern as the NSG does on uniform
-data - random 4*d-byte row gathers over the whole table - so kernel variants (EPS_TRV_WAVES, EPS_TRV_PER_CU, batch) can be
+data - random 4*d-byte row gathers over the whole table - so kernel variants (EPS_TRV_WAVES, batch) can be
 compared in seconds.  Results are not recall figures.
     python scripts/lab/bench_random_graph.py [rows] [dim] [deg] [batches e.g. 1024,2048]"""
 import json
@@ -52,5 +52,5 @@ for b in batches:
             st = ix.stats()
             alg = st["dist_evals"] * (4.0 * d + 4) + st["expansions"] * (8 + 4.0 * deg)
             km = float(np.median(ms))
-            print(json.dumps({"rows": n, "batch": b, "T": T, "waves_per_query": waves, "per_cu": os.environ.get("EPS_TRV_PER_CU", "auto"),
+            print(json.dumps({"rows": n, "batch": b, "T": T, "waves_per_query": waves,
                               "kernel_ms": km, "evals_per_query": st["dist_evals"] / b, "GBps": alg / (km * 1e-3) / 1e9, "frac_of_8TBps": alg / (km * 1e-3) / 8e12}), flush=True)

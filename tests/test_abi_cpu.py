@@ -150,7 +150,7 @@ def test_product_library_reads_no_environment_and_has_no_lab_build(built):
         assert s not in src, s
 
 
-def test_tuning_names_agree():
+def test_tuning_names_agree_on_24_switches():
     """One list of switches: the names the library's sources look up (tune_int / tune_env), the names the Python wrapper forwards
     (TUNING_NAMES) and the names the eps_set_tuning comment of the public header documents are the same set."""
     from vectordb_amd import _lib
@@ -161,7 +161,7 @@ def test_tuning_names_agree():
     hdr = open(os.path.join(ROOT, "include", "epsilla_gfx950.h")).read()
     head = hdr[:hdr.index("int32_t eps_set_tuning(")]
     documented = set(re.findall(r"EPS_[A-Z0-9_]+", head[head.rindex("/*"):])) - {"EPS_OK"}
-    assert len(used) >= 30, sorted(used)
+    assert len(used) == 24, sorted(used)
     assert used == set(_lib.TUNING_NAMES), (sorted(used - set(_lib.TUNING_NAMES)), sorted(set(_lib.TUNING_NAMES) - used))
     assert used == documented, (sorted(used - documented), sorted(documented - used))
 

@@ -353,11 +353,10 @@ def test_one_pass_search_survives_adversarial_order_and_selective_deletion(amd):
 
 
 @pytest.mark.parametrize("metric", [0, 1, 2])
-def test_a_handful_of_queries_takes_the_short_chain_and_the_split_rerank(amd, monkeypatch, metric):
+def test_a_handful_of_queries_takes_the_short_chain(amd, metric):
     """r4: 1 ... 16 queries per call run the fused launch chain (query preparation + fragment copy + start state in one launch, seed
     selection straight into the candidate lists by a 16-wavefront workgroup, finalisation in the last re-rank, 3 stages up to 4
-    queries) and every re-rank spread over 8 workgroups per query with a last-arrival merge: the same bits as the stream scan, with
-    deletions and a filter, for k = 1 / 10 / 100, and the same with the split re-rank switched off."""
+    queries): the same bits as the stream scan, with deletions and a filter, for k = 1 / 10 / 100."""
     n, d = 150_000, 192
     X, Q = data(n, d, 71), data(16, d, 72)
     X[5000:5040] = X[4999]                      # ties: equal distances, ordered by id
@@ -366,25 +365,23 @@ def test_a_handful_of_queries_takes_the_short_chain_and_the_split_rerank(amd, mo
         Q = amd.normalize_rows(Q, only_if_nonzero=False)
     Q[1] = X[5010]
     idc = np.arange(n, dtype=np.int32)
-    for split in ("1", "0"):
-        monkeypatch.setenv("EPS_RERANK_SPLIT", split)
-        ix = amd.GpuIndex(d, metric)
-        ix.attach_rows(X)
-        for setup in ("plain", "deleted + filter"):
-            if setup != "plain":
-                ix.set_deleted(bitset(n, range(3, n, 11)))
-                ix.set_int_filter(idc, ">=", 1000)
-            for nq in (1, 2, 3, 4, 5, 16):
-                for k in (1, 10, 100):
-                    a = ix.search(Q[:nq], k, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8)
-                    st = ix.stats()
-                    assert st["main_kernel_bits"] == 8 and st["overflow_queries"] == 0, (split, setup, nq, k, st)
-                    same(a, ix.search(Q[:nq], k, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM), "split %s %s nq %d k %d" % (split, setup, nq, k))
-            # the same call many times: the arrival counters are back at zero after every launch
-            first = ix.search(Q[:2], 10, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8)
-            for _ in range(20):
-                same(ix.search(Q[:2], 10, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8), first, "repeat")
-        ix.close()
+    ix = amd.GpuIndex(d, metric)
+    ix.attach_rows(X)
+    for setup in ("plain", "deleted + filter"):
+        if setup != "plain":
+            ix.set_deleted(bitset(n, range(3, n, 11)))
+            ix.set_int_filter(idc, ">=", 1000)
+        for nq in (1, 2, 3, 4, 5, 16):
+            for k in (1, 10, 100):
+                a = ix.search(Q[:nq], k, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8)
+                st = ix.stats()
+                assert st["main_kernel_bits"] == 8 and st["overflow_queries"] == 0, (setup, nq, k, st)
+                same(a, ix.search(Q[:nq], k, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM), "%s nq %d k %d" % (setup, nq, k))
+        # the same call many times: the one-pass state and the counters are back where the next call expects them after every launch
+        first = ix.search(Q[:2], 10, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8)
+        for _ in range(20):
+            same(ix.search(Q[:2], 10, mode=amd.MODE_FLAT, flat_engine=amd.FLAT_MFMA_I8), first, "repeat")
+    ix.close()
 
 
 def test_auto_stops_paying_for_an_8_bit_pass_that_never_filters(amd):

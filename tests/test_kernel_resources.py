@@ -110,5 +110,5 @@ def test_one_pass_tail_kernel_fits_a_full_workgroup(tmp_path):
         # static LDS (ids + rank slots + counters) + the dynamic part the launch asks for: the query (<= 4 KB at d <= 1024) + 4096 keys of 8 bytes
         assert u["LDS Size [bytes/block]"] + 4096 + 4096 * 8 <= 65536, (k, u)
     for k, u in usage.items():
-        if ("rerank_kernelILi1ELb1E" in k or "rerank_kernelILi2ELb1E" in k or "rerank_split_kernel" in k):
+        if ("rerank_kernelILi1ELb1E" in k or "rerank_kernelILi2ELb1E" in k):
             assert u["ScratchSize [bytes/lane]"] == 0, (k, u)

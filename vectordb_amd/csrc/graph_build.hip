@@ -468,7 +468,7 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   // error is a small fraction of the gap between the K-th and the 128-th neighbour; tests/test_gpu_build.py measures the recall).
   DevBuf knn, run, runA, candA, cntA;
   const int k1 = K + 1;
-  const int64_t B = std::max(256, tune_int("EPS_BUILD_BLOCK", 2048));   // queries per kNN pass
+  constexpr int64_t B = 2048;   // queries per kNN pass
   const bool use_mfma = n >= 65536;
   const int kA = (int)std::min<int64_t>(n, std::max(k1, 128));
   if (!knn.reserve((size_t)n * K * 4) || !run.reserve((size_t)B * k1 * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (kNN graph)");
@@ -616,7 +616,6 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   ta.rows = ix.d_rows_;
   ta.dim = dim;
   ta.metric = 0;
-  ta.off = nullptr;
   ta.nbr = knn.as<u32>();
   ta.fixed_deg = K;
   ta.init_ids = d_seeds.as<u32>();
@@ -629,7 +628,6 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   ta.words = bitmap_vis ? vis_words : 0;
   ta.ghash = ghash_vis ? visb.as<u32>() : nullptr;
   ta.hslots = ghash_vis ? GHASH_SLOTS : 0;
-  ta.out_queue = nullptr;
   ta.counters = counters.as<unsigned long long>();
   ta.counters_n = 4;
   ta.log = logb.as<u64>();
@@ -673,9 +671,9 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
       hipError_t e = hipMemsetAsync(visb.p, 0, (size_t)nb * vis_words * 4, s);
       if (e != hipSuccess) return e;
       if (vec4)
-        hipLaunchKernelGGL((traverse_kernel<true, false, true, 4>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+        hipLaunchKernelGGL((traverse_kernel<true, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
       else
-        hipLaunchKernelGGL((traverse_kernel<false, false, true, 4>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+        hipLaunchKernelGGL((traverse_kernel<false, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
     } else {
       const size_t shm = ghash_vis ? trv_shm_bm : trv_shm;   // (the LDS layout without the table)
       if (ghash_vis) {
@@ -683,9 +681,9 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
         if (e != hipSuccess) return e;
       }
       if (vec4)
-        hipLaunchKernelGGL((traverse_kernel<true, true, true, 4>), dim3((unsigned)nb), dim3(256), shm, s, ta);
+        hipLaunchKernelGGL((traverse_kernel<true, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
       else
-        hipLaunchKernelGGL((traverse_kernel<false, true, true, 4>), dim3((unsigned)nb), dim3(256), shm, s, ta);
+        hipLaunchKernelGGL((traverse_kernel<false, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
     }
     return hipSuccess;
   };

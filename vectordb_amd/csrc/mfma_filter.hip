@@ -54,8 +54,6 @@
 
 namespace eps {
 
-constexpr int EPS_MFMA_MANTISSA_DEFAULT = 10;
-
 struct HalfMirror {
   DevBuf xh;       // _Float16 [n_pad][d_pad]
   DevBuf xn;       // float [n_pad]  |x|^2 (+inf on padding rows)
@@ -73,7 +71,6 @@ struct HalfMirror {
   DevBuf cand;     // u32 [b][cap]
   DevBuf cnt;      // u32 [b] + overflow counter at [b]
   DevBuf seedc;    // u32 [b][k]: rows of the k best seeds of every query (the seed stage's candidate lists)
-  DevBuf partk, partd;   // a handful of queries: per-workgroup partial top-k lists of the split re-rank [b][8][k], arrival counters [b] (zero between launches)
   // 8-bit mirror (first-pass operand of the filter, see above)
   DevBuf x8;       // int8 [n_pad8][d_pad8]
   DevBuf acc0;     // int32 [n_pad8]: accumulator start of every row = ceil(-R/u) + 1 (-2^30 on padding rows)
@@ -138,7 +135,6 @@ struct HalfMirror {
   int d_pad = 0;
   bool fp16_range_ok = true;
   int num_cus = 0;             // CUs of this index's device (persistent grid size)
-  int drop = -1;               // low mantissa bits the mirror and the query operand leave at zero (to_half_drop)
   int64_t extended_rows = 0;   // rows converted by incremental extensions (test hook)
   float h_scal[4] = {0, 0, 0, 0};
 };
@@ -146,21 +142,6 @@ struct HalfMirror {
 void half_mirror_free(HalfMirror* m) { delete m; }
 
 // ------------------------------------------------------------------------------------------------ mirror build
-// fp32 -> fp16 keeping only the top `10 - drop` mantissa bits (round to nearest even at that width).  The MI355X clocks to its
-// power budget and the matrix pipe draws less on operands that toggle fewer bits (scripts/lab/mfma_power.hip: the same MFMA
-// stream runs 7.6 % / 12 % faster at 7 / 5 mantissa bits); the filter only needs a lower bound, and every bound below is
-// computed from the residual |x - xh| of the value actually stored, so the result stays exact for any `drop` - coarser
-// operands just let a few more candidates through to the fp32 re-rank.
-__device__ __forceinline__ _Float16 to_half_drop(float x, int drop) {
-  const _Float16 h = (_Float16)x;
-  if (drop <= 0) return h;
-  unsigned short u = __builtin_bit_cast(unsigned short, h);
-  const unsigned short keep = (unsigned short)~((1u << drop) - 1u);
-  const unsigned short r = (unsigned short)(u + ((1u << (drop - 1)) - 1u) + ((u >> drop) & 1u));   // RNE (carries into the exponent)
-  u = ((r & 0x7C00u) == 0x7C00u && (u & 0x7C00u) != 0x7C00u) ? (unsigned short)(u & keep) : (unsigned short)(r & keep);   // never round up to inf
-  return __builtin_bit_cast(_Float16, u);
-}
-
 __device__ __forceinline__ void atomic_max_pos(float* addr, float v) {  // v >= 0
   atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
@@ -169,7 +150,7 @@ __device__ __forceinline__ void atomic_max_pos(float* addr, float v) {  // v >= 
 // (the per-index maxima in `scal` only ever grow, so they are accumulated across calls)
 __global__ __launch_bounds__(256) void half_mirror_kernel(const float* rows, int64_t row0, int64_t n, int64_t n_pad, int dim, int d_pad,
                                                           _Float16* xh, float* xn, float* zeros, float* xn_s, float* zeros_s, float* scal,
-                                                          float gamma, int drop) {
+                                                          float gamma) {
   // one wavefront per row, grid-stride over rows; the four per-index maxima are reduced in registers and
   // published with ONE atomic per wavefront (an atomic per row serialises 10M rows on four addresses)
   const int lane = lane_id();
@@ -196,7 +177,7 @@ __global__ __launch_bounds__(256) void half_mirror_kernel(const float* rows, int
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < dim) x = *reinterpret_cast<const float4*>(src + c);
         half4 h;
-        h[0] = to_half_drop(x.x, drop); h[1] = to_half_drop(x.y, drop); h[2] = to_half_drop(x.z, drop); h[3] = to_half_drop(x.w, drop);
+        h[0] = (_Float16)x.x; h[1] = (_Float16)x.y; h[2] = (_Float16)x.z; h[3] = (_Float16)x.w;
         *reinterpret_cast<half4*>(dst + c) = h;
         const float xs[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
@@ -212,7 +193,7 @@ __global__ __launch_bounds__(256) void half_mirror_kernel(const float* rows, int
     } else {
       for (int c = lane; c < d_pad; c += 64) {
         const float x = c < dim ? src[c] : 0.f;
-        const _Float16 h = to_half_drop(x, drop);
+        const _Float16 h = (_Float16)x;
         const float hf = (float)h;
         dst[c] = h;
         s2 = fmaf(x, x, s2);
@@ -249,7 +230,7 @@ __global__ __launch_bounds__(256) void half_mirror_kernel(const float* rows, int
 }
 
 __global__ __launch_bounds__(256) void query_prep_kernel(const float* q, int64_t nq, int64_t b_pad, int dim, int d_pad,
-                                                         _Float16* qh, float* qstat, int drop) {
+                                                         _Float16* qh, float* qstat) {
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= b_pad) return;
   const int lane = lane_id();
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* q, int64_t
     // A component beyond the fp16 range is stored as +-65504, not +-inf: inf * 0 would make NaN accumulators that fail every
     // `acc >= T` and silently drop rows from an exact answer.  Clamped, the component's residual enters |q - qh| like any
     // other rounding error: the bound stays valid (and becomes so loose that the batch ends on the stream engine).
-    const _Float16 h = to_half_drop(fminf(fmaxf(x, -65504.f), 65504.f), drop);
+    const _Float16 h = (_Float16)fminf(fmaxf(x, -65504.f), 65504.f);
     dst[c] = h;
     s2 = fmaf(x, x, s2);
     const float e = x - (float)h;
@@ -764,11 +745,6 @@ static int32_t ensure_mirror(Index& ix) {
   if (!ix.mirror_) ix.mirror_ = new HalfMirror();
   HalfMirror& m = *ix.mirror_;
   const int64_t n = ix.n_rows_;
-  if (m.drop < 0) {   // EPS_MFMA_MANTISSA = mantissa bits the fp16 operands keep (10 = plain fp16); fixed per mirror
-    const char* e = tune_env("EPS_MFMA_MANTISSA");
-    const int keep = e ? std::min(10, std::max(2, atoi(e))) : EPS_MFMA_MANTISSA_DEFAULT;
-    m.drop = 10 - keep;
-  }
   if (m.version == ix.rows_version_ && m.n == n) return EPS_OK;
   // appended rows: only the new rows are converted; the 15 GB mirror of a 10M-row table is not rebuilt
   const bool extend = m.version == ix.rows_version_ && m.n > 0 && m.n < n;
@@ -789,7 +765,7 @@ static int32_t ensure_mirror(Index& ix) {
   const int64_t row0 = extend ? m.n : 0;
   hipLaunchKernelGGL(half_mirror_kernel, dim3((unsigned)std::min<int64_t>((n_pad - row0 + 3) / 4, 8192)), dim3(256), 0, s, ix.d_rows_, row0, n, n_pad,
                      (int)ix.dim_, d_pad, m.xh.as<_Float16>(), m.xn.as<float>(), m.zeros.as<float>(), m.xn_s.as<float>(), m.zeros_s.as<float>(),
-                     m.scal.as<float>(), gamma, m.drop);
+                     m.scal.as<float>(), gamma);
   er = hipMemcpyAsync(m.h_scal, m.scal.p, 16, hipMemcpyDeviceToHost, s);
   if (er == hipSuccess) er = hipStreamSynchronize(s);
   if (er != hipSuccess) return ix.hip_fail(er, "fp16 mirror build");
@@ -1043,8 +1019,7 @@ static int32_t ensure_mirror8(Index& ix) {
     // Per-row margins are folded per batch only where rows DIFFER: a forced row, or a residual norm beyond 1.5 x the smallest (a clamped
     // value somewhere).  On homogeneous tables (every row a plain rounding residual: within a few per cent of each other) the table-wide
     // margin in the thresholds is as tight, keeps every query's own norms, and costs no pass over the rows (10M rows: 40 us per batch).
-    m.fold8 = forced > 0 || m.h_scal8[0] > 1.5f * m.h_scal8[7] || (tune_int("EPS_MFMA_FOLD", 0) != 0);
-    if (tune_int("EPS_MFMA_FOLD", 1) == 0 && forced == 0) m.fold8 = false;
+    m.fold8 = forced > 0 || m.h_scal8[0] > 1.5f * m.h_scal8[7];
     m.extended_rows8 += extend ? n - row0 : 0;
   }
   if (!m.i8_ok) {   // nothing of it is used: give the memory back
@@ -1104,6 +1079,28 @@ void quant8_queries(Index& ix, const Quant8View& v, const float* dq, int64_t nq,
                      m.hrow.as<float>(), m.n8, m.n_pad8, m.qmax.as<u32>(), ix.metric_ == 0 ? 2.f : 1.f, 1.f / v.u, m.acc0b.as<int>());
 }
 
+// The static part of the rule for the one-pass search (stream8_kernel.hpp): the cost model below prices a call as that form exactly when
+// the engine (flat_stream8_slice) would take it up, before the state it learns at run time (declined forms, filters).  m8 = the 8-bit mirror
+// of these rows, or null while none is built; n = the rows the call scans.
+static bool one_pass_fits(const Index& ix, const HalfMirror* m8, int64_t nq, int k, int64_t n) {
+  if (tune_int("EPS_FLAT_ONE_PASS", 1) == 0) return false;
+  const int max_k = std::min(S8_MAX_K, std::max(1, tune_int("EPS_S8_MAX_K", S8_MAX_K)));   // (A/B switch: 16 = the r4 range, larger k on the staged chain)
+  // (rows of d_pad8 = 512..1024 bytes: 2..4 pieces of 256 columns)
+  if (nq < 1 || nq > S8_MAX_Q || k < 1 || k > max_k || n < 65536 || ix.dim_ > 1024 || (m8 && n > m8->n8)) return false;
+  // r6: tables whose margins are folded per batch (fold8: rows with a clamped value) take the form too - behind the prep launch and the fold
+  // launch (the margins depend on the call's queries), with margin-free thresholds and offers of `accumulator - 2 x the row's margin` (stream8_offer_value)
+  const bool fold8 = m8 && m8->fold8;
+  // (17..32 queries, r6: the two-column-block pass beats the staged chain where a query leaves a few hundred candidates - 1M x 768 U[0,1): 17 / 24 / 32
+  // queries 0.235 / 0.254 / 0.281 ms against 0.38 - and loses where it leaves several times that: the same table of embedding-like rows 0.433 /
+  // 0.465 / 0.505 against 0.432 / 0.443 / 0.443 (profiles/r6_one_pass_17_to_32_queries.txt).  Tables with folded margins are the looser ones.)
+  if (nq > 16 && fold8) return false;
+  // (... and on LARGE tables: with two column blocks the pass is no longer purely HBM-bound - 24 MFMAs and 12 LDS operand reads per 16-row block - and its
+  // time grows with the queries, while the chain's 128-query tiles stream the mirror at the HBM rate whatever nq: 10M x 768, 17 / 24 / 32 queries: 1.46 /
+  // 1.54 / 1.73 ms against the chain's 1.53; 4M: 0.66 / 0.70 / 0.79 against 0.78; 2M: 0.38 / 0.40 / 0.45 against 0.51)
+  if (nq > 16 && (double)(nq - 16) * (double)n > 64e6) return false;
+  return true;
+}
+
 bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
   // FLAT_AUTO: both engines return the same bits, so this is purely a cost decision.  The stream scan reads the fp32 rows once
   // per 4 queries; the filter reads its mirror once per <= 2048 queries - the 8-bit mirror is a quarter of the rows' bytes, the
@@ -1117,8 +1114,9 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
   const bool have8 = known8 && m->i8_ok;
   const bool can16 = !have16 || m->fp16_range_ok;
   if (known8 && !have8 && !can16) return false;                 // neither mirror can serve this table
-  // up to 16 queries, k <= 64, rows of <= 1024 bytes: the one-pass search (stream8_kernel.hpp) - one pass over d_pad8 + 4 bytes per row
-  const bool one_pass_shape = nq <= S8_MAX_Q && k <= S8_MAX_K && ix.dim_ <= 1024 && !(tune_int("EPS_FLAT_ONE_PASS", 1) == 0);
+  // up to 32 queries, k <= 64, rows of <= 1024 bytes: the one-pass search (stream8_kernel.hpp) - one pass over d_pad8 + 4 bytes per row.
+  // (an 8-bit mirror not built yet, or behind appended rows, counts as one without folded margins)
+  const bool one_pass = one_pass_fits(ix, known8 && m->n8 == ix.n_rows_ ? m : nullptr, nq, k, ix.n_rows_);
   if (nq < 8 && !have8 && !have16) {
     // single-query traffic alone does not get a mirror (n x d bytes of HBM + a pass over the table to build it) at once: r4, after 16 such
     // calls on the same rows it does, where the one-pass search can use it (0.20 ms instead of 0.62 ms per call at 1M x 768)
@@ -1126,7 +1124,7 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
       ix.small_calls_version_ = ix.rows_version_;
       ix.small_calls_ = 0;
     }
-    if (!one_pass_shape || known8 || ++ix.small_calls_ <= 16) return false;
+    if (!one_pass || known8 || ++ix.small_calls_ <= 16) return false;
   }
   const bool use8 = have8 || !known8;                            // (an 8-bit mirror would be built first)
   const double rows = (double)ix.n_rows_, d = (double)ix.dim_;
@@ -1134,37 +1132,25 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
   const double rate = use8 ? 2.0e15 : 1.2e15;                    // matrix rate the filter kernel reaches
   const double dp = use8 ? op_bytes : op_bytes / 2.0;
   const double stream_s = std::ceil((double)nq / 4.0) * rows * d * 4.0 / 6.0e12 + 0.2e-3;
-  const double filter_s = (use8 && one_pass_shape)   // (r5: filter programs take the one-pass form too - behind one mask launch; r6: so do tables with folded margins)
+  const double filter_s = (use8 && one_pass)   // (r5: filter programs take the one-pass form too - behind one mask launch; r6: so do tables with folded margins)
                               ? 0.07e-3 + rows * (std::ceil(d / 256.0) * 256.0 + 4.0) / 5.7e12
                               : 0.35e-3 + std::max(rows * op_bytes / 5.0e12, 2.0 * 128.0 * std::ceil((double)nq / 128.0) * rows * dp / rate);
   return filter_s < stream_s;
 }
 
-// A handful of queries (<= 16, k <= 64) in ONE pass over the 8-bit mirror: stream8_kernel.hpp.  *done = false: not applicable to this call,
+constexpr int S8_WG_PER_CU = 2;   // workgroups of the one-pass kernel per CU
+
+// A handful of queries (<= 32, k <= 64) in ONE pass over the 8-bit mirror: stream8_kernel.hpp.  *done = false: not applicable to this call,
 // or a list overflowed - the staged chain below answers it (results are bit-identical either way: both end in the same exact re-rank).
 static int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool* done) {
   *done = false;
   HalfMirror& m = *ix.mirror_;
   const int64_t n = ix.scan_limit_ >= 0 ? std::min(ix.scan_limit_, ix.n_rows_) : ix.n_rows_;
+  if (!one_pass_fits(ix, &m, nq, k, n)) return EPS_OK;
   const int pieces = m.d_pad8 / 256;
-  if (tune_int("EPS_FLAT_ONE_PASS", 1) == 0) return EPS_OK;
-  const int max_q = std::min(S8_MAX_Q, std::max(1, tune_int("EPS_S8_MAX_Q", S8_MAX_Q)));   // (A/B switch: 4 = the r4 form, 5+ queries on the staged chain)
-  const int max_k = std::min(S8_MAX_K, std::max(1, tune_int("EPS_S8_MAX_K", S8_MAX_K)));   // (A/B switch: 16 = the r4 range, larger k on the staged chain)
-  if (nq < 1 || nq > max_q || k < 1 || k > max_k || n < 65536 || n > m.n8 || m.d_pad8 % 256 != 0 || pieces < 2 || pieces > 4) return EPS_OK;
-  // r6: tables whose margins are folded per batch (m.fold8: rows with a clamped value) take the form too - behind the prep launch and the fold
-  // launch (the margins depend on the call's queries), with margin-free thresholds and offers of `accumulator - 2 x the row's margin` (stream8_offer_value)
-  const bool fold = m.fold8 && tune_int("EPS_S8_FOLD", 1) != 0;   // (A/B switch: 0 = such tables on the staged chain, as until r6)
-  if (m.fold8 && !fold) return EPS_OK;
-  // (17..32 queries, r6: the two-column-block pass beats the staged chain where a query leaves a few hundred candidates - 1M x 768 U[0,1): 17 / 24 / 32
-  // queries 0.235 / 0.254 / 0.281 ms against 0.38 - and loses where it leaves several times that: the same table of embedding-like rows 0.433 /
-  // 0.465 / 0.505 against 0.432 / 0.443 / 0.443 (profiles/r6_one_pass_17_to_32_queries.txt).  Tables with folded margins are the looser ones.)
-  if (nq > 16 && m.fold8 && tune_int("EPS_S8_MAX_Q", 0) == 0) return EPS_OK;
-  // (... and on LARGE tables: with two column blocks the pass is no longer purely HBM-bound - 24 MFMAs and 12 LDS operand reads per 16-row block - and its
-  // time grows with the queries, while the chain's 128-query tiles stream the mirror at the HBM rate whatever nq: 10M x 768, 17 / 24 / 32 queries: 1.46 /
-  // 1.54 / 1.73 ms against the chain's 1.53; 4M: 0.66 / 0.70 / 0.79 against 0.78; 2M: 0.38 / 0.40 / 0.45 against 0.51)
-  if (nq > 16 && (double)(nq - 16) * (double)n > 64e6 && tune_int("EPS_S8_MAX_Q", 0) == 0) return EPS_OK;
-  // (r6: ... and per kernel form - five or more queries share one list budget per query and overflow on tables where one query does not:
-  // an 8-query batch must not talk the table out of the form for single-query traffic)
+  const bool fold = m.fold8;
+  // (a form that overflowed twice in a row on these rows stays on the chain - per kernel form, r6: five or more queries share one list budget per
+  // query and overflow on tables where one query does not: an 8-query batch must not talk the table out of the form for single-query traffic)
   const int kclass = (k <= 16 ? 0 : 1) + (nq <= 4 ? 0 : (nq <= 16 ? 2 : 4));   // (r6: 17..32 queries - two column blocks - are a form of their own)
   if (m.s8_declined_version[kclass] == ix.rows_version_) return EPS_OK;
   FilterSpec fs = ix.filter_spec();
@@ -1256,8 +1242,7 @@ static int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k,
     m.s8_cus = hipGetDeviceProperties(&prop, ix.device_) == hipSuccess ? std::max(8, prop.multiProcessorCount) : 256;
   }
   const int cus = m.s8_cus;
-  const int wg_per_cu = std::max(1, tune_int("EPS_S8_WG_PER_CU", 2));
-  const dim3 grid((unsigned)std::min<int64_t>(std::min<int64_t>((int64_t)cus * wg_per_cu, S8_MAX_WAVES / 4), (n + 63) / 64)), block(256);
+  const dim3 grid((unsigned)std::min<int64_t>(std::min<int64_t>((int64_t)cus * S8_WG_PER_CU, S8_MAX_WAVES / 4), (n + 63) / 64)), block(256);
   a.waves = (int)grid.x * 4;
   // (no event pair around the pass by default: a record between two dependent launches costs this chain 5-10 us each; kernel_ms covers
   // the call.  EPS_ONE_PASS_TIMED=1 - bench.py's roofline leg - records the pair: main_kernel_ms = the pass)
@@ -1486,7 +1471,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
                          m.hrow.as<float>(), m.n8, m.n_pad8, m.qmax.as<u32>(), ix.metric_ == 0 ? 2.f : 1.f, 1.f / u8, m.acc0b.as<int>());
   } else {
     hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)((b_pad + 3) / 4)), dim3(256), 0, s, dq, nq, b_pad, (int)ix.dim_,
-                       m.d_pad, m.qh.as<_Float16>(), m.qstat.as<float>(), m.drop);
+                       m.d_pad, m.qh.as<_Float16>(), m.qstat.as<float>());
   }
   const _Float16* q_op = i8 ? reinterpret_cast<const _Float16*>(m.q8.p) : m.qh.as<_Float16>();   // the query operand, row-major
   if (version >= 7 && !prep_does_it_all)
@@ -1507,8 +1492,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
     // d = 768); S stages with equal ratios (n / S0)^(1/S) cost S * k * c * (n / S0)^(1/S) candidates and S times the per-stage
     // overhead (launch tails + one re-rank launch, ~0.1 ms at 10M rows).  A candidate costs its wavefront ~900 cycles in the
     // filter's epilogue and 3 KB of gather in the re-rank, so the looser 8-bit bound wants more, smaller steps (measured at
-    // 10M x 768, batch 1024: EPS_MFMA_STAGES sweep in profiles/r3_stage_sweep.txt).
-    const char* st_env = tune_env("EPS_MFMA_STAGES");
+    // 10M x 768, batch 1024: the stage-count sweep in profiles/r3_stage_sweep.txt).
     // Few queries (<= 64): 4 stages.  A call is then a chain of short dependent launches (profiles/r3_single_query_timeline.txt: one
     // query on 1M x 768 = 400 us of back-to-back kernels, 185 us of them the filter stages streaming the mirror once, 110 us seven
     // one-workgroup re-ranks), and two re-ranks less beat the longer lists: scripts/lab/stages_by_batch.py, 1M x 768, p50 ms at
@@ -1519,7 +1503,6 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
     int nstages = i8 ? (nq <= 4 ? 3 : (nq <= 64 ? 4 : 6)) : 3;
     if (i8)   // ... but never so few that a stage's expected k * c * ratio candidates come near the list capacity
       while (nstages < 8 && (double)k * 5.0 * std::pow((double)n / (double)S0, 1.0 / (double)nstages) > 0.5 * (double)cap) ++nstages;
-    if (st_env) nstages = std::min(8, std::max(1, atoi(st_env)));
     const double r = std::max(i8 ? 3.0 : 4.0, std::pow((double)n / (double)S0, 1.0 / (double)nstages));
     // stage boundaries on multiples of the rows one "round" of the persistent grid covers (256 workgroups x 256 rows /
     // query tiles), so the small stages do not end on a mostly idle round
@@ -1603,20 +1586,6 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   ra.u = u8;
   ra.slack = 0.f;   // (set below, with the stages)
   ra.gsync = m.gsync.as<u32>();
-  if (!approx && nq <= 16 && k <= 128 && tune_int("EPS_RERANK_SPLIT", 0) != 0) {
-    // a handful of queries: every re-rank spread over 8 workgroups per query (RerankArgs::parts).  Opt-in: measured, it takes 5 us off a
-    // 340 us single-query call (profiles/r4_single_query_latency.txt) - a re-rank of ~150 rows is a chain of dependent latencies, not a
-    // bandwidth problem - and is not worth a cross-workgroup hand-off on the default path
-    const bool fresh = m.partd.cap < (size_t)nq * 4;
-    if (!m.partk.reserve((size_t)nq * 8 * k * 8) || !m.partd.reserve((size_t)64 * 4)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
-    if (fresh) {
-      const hipError_t e0 = hipMemsetAsync(m.partd.p, 0, m.partd.cap, s);
-      if (e0 != hipSuccess) return ix.hip_fail(e0, "memset");
-    }
-    ra.parts = 8;
-    ra.part_keys = m.partk.as<u64>();
-    ra.part_done = m.partd.as<u32>();
-  }
 
   const int bm = BM3;   // every kernel generation works on 256-row tiles
   const size_t shm = version >= 7 ? V7_LDS_BYTES : 2 * 65536 + 2 * 256 * sizeof(float);
@@ -1635,7 +1604,6 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V7_LDS_BYTES);
   }
   const int num_cus = m.num_cus;
-  const bool narrow_env = !(tune_int("EPS_MFMA_NARROW", 1) == 0);
   auto launch_filter = [&](const FilterArgs& f) {
     {
       FilterArgs f3 = f;
@@ -1651,7 +1619,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
     else if (mode == FM_KEYS) hipLaunchKernelGGL((mfma_filter_kernel_v7<JQ_, FM_KEYS, I8_>), grid, block, shm, s, f3);      \
     else hipLaunchKernelGGL((mfma_filter_kernel_v7<JQ_, FM_IDS, I8_>), grid, block, shm, s, f3);                            \
   } while (0)
-        if (nq <= 128 && narrow_env) {   // one 128-query tile: half the padded MFMA work, the pass streams the mirror
+        if (nq <= 128) {   // one 128-query tile: half the padded MFMA work, the pass streams the mirror
           f3.tiles_q = 1;
           if (i8) EPS_LAUNCH_V7(1, true); else EPS_LAUNCH_V7(1, false);
         } else {
@@ -1872,10 +1840,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
 int32_t flat_mfma_search(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool approx, int bits) {
   if (ix.n_rows_ <= 0) return ix.flat_stream(dq, nq, k, 0, 0, run_keys, false);   // (nothing to mirror)
   const bool auto_bits = bits != 8 && bits != 16;
-  if (auto_bits) {   // the library's choice: 8-bit first pass unless switched off (EPS_MFMA_BITS=16, A/B) - tables it cannot serve fall back by themselves
-    const char* e = tune_env("EPS_MFMA_BITS");
-    bits = (e && atoi(e) == 16) ? 16 : 8;
-  }
+  if (auto_bits) bits = 8;   // the library's choice: 8-bit first pass - tables it cannot serve fall back by themselves
   const int64_t slice = std::max(256, tune_int("EPS_MFMA_MAX_BATCH", 2048));
   if (nq <= slice) return flat_mfma_search_slice(ix, dq, nq, k, run_keys, approx, 1, bits, auto_bits);
   for (int64_t q0 = 0; q0 < nq; q0 += slice) {   // the counters in ix.stats_ accumulate over the slices

@@ -333,8 +333,7 @@ int32_t graph_search_impl(Index& ix, const float* dq, int64_t nq, int k, const e
   // wavefronts per query, two queries per CU (T = 4, L = 2000, batch 1024: 1M x 768 46.6 -> 39.4 ms, 10M-row proxy 56.8 -> 49.3 ms;
   // 4 wavefronts 64.6, 16 wavefronts 66.1), and 8 wavefronts also beat the 4 that queues in HBM used to get (L = 4000: 126.6 ->
   // 93.6 ms, L = 8000: 350.8 -> 246.7 ms).  A handful of queries (<= 256, latency) keeps the one-workgroup-per-CU form.
-  const int lds_kb = tune_int("EPS_TRV_LDS_KB", 0);   // (A/B knob)
-  const size_t lds_limit = lds_kb > 0 ? (size_t)std::max(16, lds_kb) * 1024 : (nq <= 256 ? (size_t)150 * 1024 : (size_t)80 * 1024);
+  const size_t lds_limit = nq <= 256 ? (size_t)150 * 1024 : (size_t)80 * 1024;
   const bool qglobal = lds_need > lds_limit;
   const bool one_per_cu = !qglobal && lds_need > (size_t)80 * 1024;
   const size_t shm = traverse2_lds_bytes((int)ix.dim_, T, (int)Lq, qtot, dp, qglobal, prefilter, q8v.cols8);
@@ -350,7 +349,6 @@ int32_t graph_search_impl(Index& ix, const float* dq, int64_t nq, int k, const e
   if (er != hipSuccess) return ix.hip_fail(er, "device properties");
   const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   int per_cu = (int)std::min<size_t>((size_t)(16 / nw), (size_t)(160 * 1024) / shm);   // 4 wavefronts per SIMD at this register use (~104 VGPRs)
-  if (const char* pc = tune_env("EPS_TRV_PER_CU")) per_cu = std::max(1, atoi(pc));
   if (per_cu < 1) per_cu = 1;
   const int64_t words = (n + 31) / 32;
   int64_t slots = std::min<int64_t>(nq, (int64_t)cus * per_cu);

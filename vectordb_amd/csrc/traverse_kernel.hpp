@@ -1,6 +1,6 @@
-// Device traversal kernel shared by the search path (traverse.hip) and the graph build (graph_build.hip).
-// See traverse.hip for the mapping to VecSearchExecutor::SearchImpl (vec_search_executor.cpp:518-715) and
-// graph_build.hip for its use as NsgIndex::GetNeighbors (nsg.cpp:158-268).
+// Device traversal kernel of the graph build (graph_build.hip): NsgIndex::GetNeighbors (nsg.cpp:158-268), the best-first
+// search of the Link step on the kNN graph, which logs the L closest nodes it evaluated for SyncPrune.  (The search path's
+// traversal is traverse2_kernel.hpp.)
 #pragma once
 #include "kernels.hpp"
 
@@ -11,8 +11,7 @@ struct TraverseArgs {
   const float* rows;
   int dim;
   int metric;
-  const int64_t* off;   // CSR offsets, or null when fixed_deg > 0
-  const u32* nbr;       // CSR neighbours, or [n][fixed_deg] lists padded with 0xFFFFFFFF
+  const u32* nbr;       // [n][fixed_deg] neighbour lists padded with 0xFFFFFFFF
   int fixed_deg;
   const u32* init_ids;
   const float* queries;
@@ -23,12 +22,11 @@ struct TraverseArgs {
   int M;       // expansions per round
   u32* visited;      // BITMAP mode: [gridDim.x][words] in HBM
   int64_t words;
-  u64* out_queue;    // [nq][L] (may be null)
   unsigned long long* counters;  // [0] distance evals, [1] expansions, [2] (counters_n > 2) searches that filled the visited hash
   int counters_n;
   u32* ghash;        // HASHVIS: non-null = the visited hash lives in HBM, [gridDim.x][hslots] u32, pre-set to 0xFF bytes by the host
   int hslots;        //          (power of two); null = TRV_HASH slots in LDS
-  u64* log;          // LOG mode: [nq][log_cap] plain (dist,id) keys: the final queue = the L closest evaluated nodes, ascending
+  u64* log;          // [nq][log_cap] plain (dist,id) keys: the final queue = the L closest evaluated nodes, ascending
   u32* log_cnt;      // [nq]
   int log_cap;       // >= L
   // exact 8-bit lower-bound prefilter of step 3 (same test as traverse2_kernel's step d0); x8 == null: off
@@ -77,11 +75,10 @@ __device__ __forceinline__ bool visit(u32* vis, u32* hash, int* hcount, u32 id, 
   }
 }
 
-// NW = wavefronts per workgroup (4: many queries in flight; 16: one query spread over a whole CU's worth of waves,
-// so the ~50 candidate rows of an expansion are all in flight at once — single-query latency)
-template <bool VEC4, bool HASHVIS, bool LOG, int NW>
-__global__ __launch_bounds__(NW * 64) void traverse_kernel(TraverseArgs a) {
-  constexpr int NT = NW * 64;
+// one workgroup of 4 wavefronts per search (many searches in flight)
+template <bool VEC4, bool HASHVIS>
+__global__ __launch_bounds__(256) void traverse_kernel(TraverseArgs a) {
+  constexpr int NW = 4, NT = NW * 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int dim = a.dim;
   const int qstride = (dim + 3) & ~3;
@@ -119,15 +116,17 @@ __global__ __launch_bounds__(NW * 64) void traverse_kernel(TraverseArgs a) {
   const int RPW8 = 64 / G8;
   u32* vis = HASHVIS ? nullptr : a.visited + q * a.words;
   unsigned long long evals = 0, expansions = 0;
-  u64* qlog = LOG ? a.log + q * (int64_t)a.log_cap : nullptr;
+  u64* qlog = a.log + q * (int64_t)a.log_cap;
   if (HASHVIS) {
     if (!a.ghash)
       for (int i = tid; i < TRV_HASH; i += NT) hash[i] = TRV_NONE;
     if (tid == 0) sh[6] = 0;
   }
-  if (LOG && tid == 0) sh[7] = 0;
-  if (tid == 0) sh[43] = 0;   // (read again by thread 0 only)
-  if (HASHVIS || LOG) __syncthreads();
+  if (tid == 0) {
+    sh[7] = 0;
+    sh[43] = 0;   // (read again by thread 0 only)
+  }
+  __syncthreads();
 
   for (int i = tid; i < qstride; i += NT) sq[i] = i < dim ? a.queries[q * dim + i] : 0.f;
   if (pf) {
@@ -217,7 +216,7 @@ __global__ __launch_bounds__(NW * 64) void traverse_kernel(TraverseArgs a) {
       int acc = 0;
       for (int i = 0; i < nsel; ++i) {
         sh[24 + i] = acc;
-        acc += a.fixed_deg > 0 ? a.fixed_deg : (int)(a.off[sh[8 + i] + 1] - a.off[sh[8 + i]]);
+        acc += a.fixed_deg;
       }
       sh[24 + nsel] = acc;
     }
@@ -239,7 +238,7 @@ __global__ __launch_bounds__(NW * 64) void traverse_kernel(TraverseArgs a) {
         if (tid < TRV_CHUNK && e < total_edges) {
           int i = 0;
           while (i + 1 < nsel && sh[24 + i + 1] <= e) ++i;
-          const int64_t rowbase = a.fixed_deg > 0 ? (int64_t)sh[8 + i] * a.fixed_deg : a.off[sh[8 + i]];
+          const int64_t rowbase = (int64_t)sh[8 + i] * a.fixed_deg;
           nb = a.nbr[rowbase + (e - sh[24 + i])];
           fresh = nb != TRV_NONE && visit<HASHVIS>(vis, hash, &sh[6], nb, hash_open, hbits);
         }
@@ -404,25 +403,21 @@ __global__ __launch_bounds__(NW * 64) void traverse_kernel(TraverseArgs a) {
     // new candidate landed there (handled via r_min above)
     __syncthreads();
   }
-  if (a.out_queue)
-    for (int i = tid; i < L; i += NT) a.out_queue[q * L + i] = queue[i];
-  if (LOG) {
-    // the log = the final queue: the L closest evaluated nodes in ascending (dist, id) order.  (Until r2 every evaluation was
-    // appended to a global list of 3840 entries, which EVERY Link search of a 768-d table overran - what got logged were the
-    // nodes met first, i.e. the far ones.)  With L >= candidate_pool_size this is all SyncPrune's depth-limited SelectEdge can see.
-    int cnt = 0;
-    for (int i = tid; i < L; i += NT) {
-      const u64 k2 = queue[i];
-      if (k2 != KEY_EMPTY) {
-        qlog[i] = ((k2 >> 32) << 32) | ((k2 >> 1) & 0x7FFFFFFFull);
-        ++cnt;
-      }
+  // the log = the final queue: the L closest evaluated nodes in ascending (dist, id) order.  (Until r2 every evaluation was
+  // appended to a global list of 3840 entries, which EVERY Link search of a 768-d table overran - what got logged were the
+  // nodes met first, i.e. the far ones.)  With L >= candidate_pool_size this is all SyncPrune's depth-limited SelectEdge can see.
+  int cnt = 0;
+  for (int i = tid; i < L; i += NT) {
+    const u64 k2 = queue[i];
+    if (k2 != KEY_EMPTY) {
+      qlog[i] = ((k2 >> 32) << 32) | ((k2 >> 1) & 0x7FFFFFFFull);
+      ++cnt;
     }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if (lane == 0) atomicAdd(&sh[7], cnt);
-    __syncthreads();
-    if (tid == 0) a.log_cnt[q] = (u32)sh[7];
   }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if (lane == 0) atomicAdd(&sh[7], cnt);
+  __syncthreads();
+  if (tid == 0) a.log_cnt[q] = (u32)sh[7];
   if (tid == 0) {
     atomicAdd(&a.counters[0], evals);
     atomicAdd(&a.counters[1], expansions);
