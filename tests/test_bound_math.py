@@ -1,5 +1,5 @@
 """The 8-bit lower bound, checked as arithmetic on the CPU (no GPU): a numpy restatement of what colmean_kernel / quant_mirror_kernel /
-query_prep8_kernel / stage_threshold8 (vectordb_amd/csrc/mfma_filter.hip, device_common.hpp) compute, in float32 where the device
+query_prep8_kernel / stage_threshold8 (vectordb_amd/csrc/mirror_build.hip, mfma_filter.hip, device_common.hpp) compute, in float32 where the device
 uses float32, and the one property every user of the mirror relies on - the flat engine's filter stages, the traversal's and the
 build searches' prefilter:
 
@@ -424,7 +424,7 @@ def test_start_up_wait_reads_a_median_offer_not_the_worst(k, slots):
 
 
 # ------------------------------------------------------------------------------------------------ r6: the grid in a rotated frame
-# (device_common.hpp rot256_load, mfma_filter.hip ensure_mirror8).  Rows and queries are quantised as y = R x, R = blockdiag(H_256 / 16) . S . P
+# (device_common.hpp rot256_load, mirror_build.hip ensure_mirror8).  Rows and queries are quantised as y = R x, R = blockdiag(H_256 / 16) . S . P
 # (a fixed permutation of the zero-padded columns, signs, a 256-point Walsh-Hadamard transform per 256-column block): R is exactly orthogonal,
 # distances do not change, and every y column is a signed mean of 256 values of the row - no column dominates, the step shrinks to what the
 # row's norm needs.  The transform runs in fp64, y - mu is rounded to fp32 once.

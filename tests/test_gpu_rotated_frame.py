@@ -1,4 +1,4 @@
-"""r6: the 8-bit mirror in a ROTATED frame (vectordb_amd/csrc/device_common.hpp rot256_load, mfma_filter.hip ensure_mirror8; arithmetic restated
+"""r6: the 8-bit mirror in a ROTATED frame (vectordb_amd/csrc/device_common.hpp rot256_load, mirror_build.hip ensure_mirror8; arithmetic restated
 and proven in tests/test_bound_math.py).  The frame may only change how many rows the 8-bit test lets through - never an answer: every user
 of the mirror (the staged matrix filter, the one-pass search, the traversal's prefilter, appended rows) must return the fp32 stream scan's
 bits (`BruteForceSearch`, reference engine/db/execution/vec_search_executor.cpp:717-768) in either frame, and the library's own choice must

@@ -14,20 +14,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="needs hipcc")
 def test_shipped_filter_kernels_do_not_spill(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-I" + os.path.join(ROOT, "include"),
-                        "-c", os.path.join(ROOT, "vectordb_amd", "csrc", "mfma_filter.hip"), "-o", str(tmp_path / "mf.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    # the flat matrix engine's three units: the staged chain (v7, v3), the one-pass search (stream8, stream8m, filter_mask), the mirror build
     usage = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    for unit in ("mfma_filter", "one_pass", "mirror_build"):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-I" + os.path.join(ROOT, "include"),
+                            "-c", os.path.join(ROOT, "vectordb_amd", "csrc", unit + ".hip"), "-o", str(tmp_path / (unit + ".o")),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        name = None
+        for line in r.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                assert name not in usage, "%s is compiled into two units (-fno-gpu-rdc: it would ship twice); the second: %s" % (name, unit)
+                usage[name] = {}
+            m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+            if m and name:
+                usage[name][m.group(1)] = int(m.group(2))
     v7 = {k: v for k, v in usage.items() if "mfma_filter_kernel_v7" in k}
     # {128, 256}-query tiles x {ids, keys, dense} epilogues x {fp16, int8} operands
     assert len(v7) == 12, list(usage)

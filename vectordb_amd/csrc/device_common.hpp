@@ -19,6 +19,17 @@ using u32 = unsigned int;
 
 constexpr u64 KEY_EMPTY = ~0ull;
 
+// Layouts that more than one translation unit relies on: the mirror build, the query preparation and the search kernels read them from here.
+constexpr int BK = 64;                        // K-step of every kernel generation
+constexpr int ROWPAD = 256;                   // mirror rows are padded to this
+// the one-pass search's table of best accumulators and its per-wavefront candidate lists (stream8_kernel.hpp)
+constexpr int S8_EMPTY = -2147483647 - 1;
+constexpr int S8_SLOTS = 64, S8_SLOTS_WIDE = 128, S8_SLOT_STRIDE = 64;   // (stride in 4-byte words)
+constexpr int S8_MAX_K = 64;   // k of a one-pass call: <= 16 with 64 slots per query, 17..64 with 128 (r5)
+constexpr int S8_MAX_Q = 32;   // queries of a one-pass call: <= 4 on v_dot4 (stream8_kernel), 5..16 on the matrix cores (stream8m_kernel, r5), 17..32 on two column blocks (r6)
+constexpr int S8_TABLE_WORDS = S8_MAX_Q * S8_SLOTS_WIDE * S8_SLOT_STRIDE;
+constexpr int S8_WAVE_CAP = 32, S8_MAX_WAVES = 8192;   // (32: a run of identical rows - 16 of them in one chunk - must not fill a list by itself)
+
 // One instruction of a compiled filter (eps_filter_op in include/epsilla_gfx950.h): a postfix program over the packed
 // attribute row of a candidate, evaluated on a small stack of doubles exactly as ExprEvaluator::NumEvaluate /
 // LogicalEvaluate do (query/expr/expr_evaluator.cpp:127-258: every number is a double, booleans are 0 / 1).

@@ -71,7 +71,7 @@ const char* tune_env(const char* name);
 int tune_int(const char* name, int dflt);
 
 struct BuildStage;   // stage-level entry of the graph build (below)
-struct Quant8View {   // the table's 8-bit mirror as other kernels see it (mfma_filter.hip)
+struct Quant8View {   // the table's 8-bit mirror as other kernels see it (mirror_build.hip)
   const signed char* x8 = nullptr;
   const int* acc0 = nullptr;
   const float* scal8 = nullptr;
@@ -83,7 +83,7 @@ struct Quant8View {   // the table's 8-bit mirror as other kernels see it (mfma_
   int64_t epoch8 = 0;     // counts the mirror's (re)builds: row constants copied elsewhere (the graph's edge constants) are stale when it moves
   bool per_batch = false; // acc0 carries per-batch margins (fold8): it changes with every batch of queries
 };
-struct HalfMirror;   // fp16 mirror + per-row bounds for the MFMA filter engine (mfma_filter.hip)
+struct HalfMirror;   // fp16 + 8-bit mirrors and per-row bounds for the MFMA filter engine (mirror.hpp, built in mirror_build.hip)
 struct GraphDev;     // device CSR + traversal scratch (traverse.hip)
 
 // What the C ABI dispatches to: one device index, or a group of them over a hash-sharded table (shard_group.cpp).

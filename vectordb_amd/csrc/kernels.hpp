@@ -31,7 +31,7 @@ void launch_flat_scan(const FlatScanArgs& a, hipStream_t s);
 // merge the `slots` keys of each query (plus, if merge_run, the existing run_keys[q][k]) into run_keys[q][k].
 // counts (optional): per-query number of valid keys at the front of its slots (candidate lists).
 // seed_cand != null (the MFMA engine's seed stage, r4): instead of the k best keys, their ROWS go to seed_cand[q][0 .. count) (sample
-// indices mapped by seed_row), seed_cnt[q] = count and run_keys[q] is left EMPTY - what seed_to_cand_kernel did in a launch of its own
+// indices mapped by seed_row), seed_cnt[q] = count and run_keys[q] is left EMPTY - no launch of its own between the seed pass and its re-rank
 void launch_merge_lists(const u64* keys, int slots, int k, int64_t nq, u64* run_keys, bool merge_run, hipStream_t s,
                         const u32* counts = nullptr, const FilterSpec* visible = nullptr, u64 id_stride = 0, u32 id_head = 0,
                         u32* seed_cand = nullptr, int seed_cap = 0, u32* seed_cnt = nullptr);

@@ -14,8 +14,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 64;                        // K-step of every kernel generation
-constexpr int ROWPAD = 256;                   // mirror rows are padded to this
 
 // ------------------------------------------------------------------------------------------------ filter kernel
 struct FilterArgs {

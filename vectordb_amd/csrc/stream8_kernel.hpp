@@ -29,7 +29,7 @@
 // junk to a few hundred entries); the selection step (below) drops it against the FINAL table without touching a
 // row, and the ordinary re-rank kernel (flat_kernels.hip) computes the survivors' exact fp32 distances, applies the deleted bitset /
 // int-column filter (calls with a compiled filter PROGRAM take the staged chain), and writes the caller-visible result.  Overflow of either list is reported through the re-rank's overflow counter and the
-// caller repeats the batch on the staged chain.  Rows with a FORCED start value (mfma_filter.hip: ACC_FORCE) are always candidates and
+// caller repeats the batch on the staged chain.  Rows with a FORCED start value (mirror_build.hip: ACC_FORCE) are always candidates and
 // never enter the table.
 #pragma once
 #include "device_common.hpp"
@@ -65,12 +65,6 @@ struct Stream8Args {
 };
 
 constexpr int S8_FORCE_LIMIT = 0x30000000;   // (= TQ_MAX8: accumulators at or above it belong to forced rows)
-constexpr int S8_EMPTY = -2147483647 - 1;
-constexpr int S8_SLOTS = 64, S8_SLOTS_WIDE = 128, S8_SLOT_STRIDE = 64;   // (stride in 4-byte words)
-constexpr int S8_MAX_K = 64;   // k of a one-pass call: <= 16 with 64 slots per query, 17..64 with 128 (r5)
-constexpr int S8_MAX_Q = 32;   // queries of a one-pass call: <= 4 on v_dot4 (stream8_kernel), 5..16 on the matrix cores (stream8m_kernel, r5), 17..32 on two column blocks (r6)
-constexpr int S8_TABLE_WORDS = S8_MAX_Q * S8_SLOTS_WIDE * S8_SLOT_STRIDE;
-constexpr int S8_WAVE_CAP = 32, S8_MAX_WAVES = 8192;   // (32: a run of identical rows - 16 of them in one chunk - must not fill a list by itself)
 
 // upper bound of the exact fp32 distance of a row whose accumulator is `acc` (see the header; mirrors stage_threshold8 term by term)
 __device__ __forceinline__ float stream8_ub(int acc, const float* qs, const float* sc, int metric, float u, float slack) {
@@ -132,7 +126,7 @@ __device__ __forceinline__ int stream8_startup_need(int k, int slots) {
   return want < most ? want : most;
 }
 
-// one query, one wavefront: the arithmetic of query_prep8_kernel (mfma_filter.hip) term by term, the bytes to `dst`, the four constants to `qs`
+// one query, one wavefront: the arithmetic of query_prep8_kernel (mirror_build.hip) term by term, the bytes to `dst`, the four constants to `qs`
 __device__ __forceinline__ void stream8_prep_query(const float* src, int dim, int d_pad8, const float* mu, float step, float inv_step, int metric, int lane,
                                                    signed char* dst, float* qs, float* qs2) {
   float s2 = 0.f, e2 = 0.f, c2 = 0.f, qm = 0.f;

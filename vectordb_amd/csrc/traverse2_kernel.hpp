@@ -64,7 +64,7 @@ struct Trv2Args {
   u64* elog;                     // [nq][elog_cap] or null
   u32* elog_cnt;                 // [nq] evaluations of the query (may exceed elog_cap: only the first elog_cap are stored)
   int elog_cap;
-  // exact lower-bound prefilter of step d on the table's 8-bit mirror (mfma_filter.hip: one grid per table, integer dot product,
+  // exact lower-bound prefilter of step d on the table's 8-bit mirror (mirror_build.hip: one grid per table, integer dot product,
   // the row constant folded into acc0): a neighbour whose 768-byte mirror row PROVES `dist > bound` is dropped without its fp32
   // row ever being read; every other neighbour goes through the unchanged fp32 evaluation.  Results are bit-identical with or
   // without it (the proof is the flat engine's: device_common.hpp stage_threshold8).  x8 == null: off.
