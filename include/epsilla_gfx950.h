@@ -288,6 +288,61 @@ int32_t eps_index_knn_graph(eps_index* h, int64_t n, const eps_build_params* p, 
  * navigation_point < 0: the closest row to the centroid (reported in *nav_out).  out_ids [n][out_degree] (-1 padded), out_deg [n]. */
 int32_t eps_index_link(eps_index* h, int64_t n, const int64_t* knn, int64_t navigation_point, const eps_build_params* p, int64_t* out_ids,
                        int32_t* out_deg, int64_t* nav_out);
+/* Two stages of the flat matrix engine on their own (r7), so that a test can hand the device and an fp64 reference identical inputs
+ * (tests/mirror_ref.py, tests/test_gpu_mirror_pin.py).  Single-device indices only; host arrays; nothing a later search could see changes
+ * (statistics, engine choices) - a mirror that a search would have built is built.
+ *
+ * A view of a mirror: builds or extends the mirror of width `bits` (8 | 16) exactly as a search would, prepares the nq <= 2048 queries exactly
+ * as the staged chain would (8-bit: on the table's grid and in its frame, with the table's own fold decision), and copies what the kernels read
+ * into the host buffers that are not NULL.  The scalars are always filled in: call once with every buffer NULL for the sizes.  Per-row buffers
+ * hold n_pad rows (the padding rows included), x holds n_pad x d_pad elements (8-bit: int8 codes; 16: fp16), q holds nq x d_pad.
+ *   8-bit: x, acc0, erow, hrow, mu [d_pad], sp [d_pad] (rotated frame only: source column, bit 31 = negative sign), scal [8], scalf [8] (scal
+ *          with the two margin entries zeroed: what thresholds of folded launches read), q, qstat [nq][4]; when the table folds: acc0b (the start
+ *          values with THIS batch's per-row margins) and qmax [2] (float bits of the batch's largest |q'| and |q' - qh'|).  usable = 0: the table
+ *          does not fit one grid, nothing is copied.
+ *   fp16:  x, xn (|x|^2), start (the accumulators' start values: -|x|^2 / 2 for L2, 0 otherwise, -inf on padding rows), scal [4], q, qstat. */
+typedef struct eps_mirror_view {
+  int64_t n, n_pad;          /* out: rows mirrored; rows of the padded mirror                                              */
+  int64_t forced_rows;       /* out, 8-bit: rows whose constant leaves the accumulator's range (always passed)             */
+  int64_t extended_rows;     /* out: rows converted by extensions after an append                                          */
+  int32_t d_pad;             /* out: elements per mirror row                                                               */
+  int32_t usable;            /* out: the table has a usable mirror of this width (8: one grid fits; 16: values in range)   */
+  int32_t rot, rot_w, fold;  /* out, 8-bit: rotated frame, columns it covers, per-row margins folded per batch             */
+  int32_t version;           /* out (nq > 0): filter kernel the chain launches for this shape, 3 | 7                       */
+  float step;                /* out, 8-bit: the grid's step                                                                */
+  float slack;               /* out: relative fp32 allowance of the thresholds (rerank_slack)                              */
+  void* x;
+  int32_t* acc0;
+  int32_t* acc0b;
+  float* erow;
+  float* hrow;
+  float* mu;
+  int32_t* sp;
+  float* scal;
+  float* scalf;
+  uint32_t* qmax;
+  float* xn;
+  float* start;
+  void* q;
+  float* qstat;
+} eps_mirror_view;
+int32_t eps_index_mirror_view(eps_index* h, int32_t bits, const float* queries, int64_t nq, eps_mirror_view* view);
+/* One filter pass with imposed thresholds: plan_chain -> prepare_queries -> thresholds -> ONE launch of the filter kernel over rows
+ * [row_lo, row_hi) (row_lo a multiple of 256, row_hi <= rows) with the arguments the chain itself would build (v3 / v7, 128- or 256-query tiles,
+ * group counters, folded start values); no re-rank, no fall-back.  mode: EPS_PASS_IDS (exact mode's lists of row ids, uint32), EPS_PASS_KEYS
+ * (approx mode's (approximate distance, row) keys, uint64: order-preserving image of the fp32 distance << 32 | row) or EPS_PASS_DENSE (the seed
+ * pass: the key of EVERY row of the range in slot row - row_lo, no test; v7 shapes, cap >= row_hi - row_lo).  thr: one value per query -
+ * EPS_THR_RAW: T in the kernel's own unit (int32 for 8-bit operands: a row passes iff its accumulator >= T; float for fp16: iff its approximate key
+ * <= T), used as it is; EPS_THR_DISTANCE: a distance (float), turned into T by the device as a stage's k-th best key would be, with the table's own
+ * choice of maxima.  T_out [nq] (may be NULL): the T used.  cnt_out [nq]: rows that passed (counted beyond cap); cand_out [nq][cap]: the first
+ * min(cnt, cap) entries of every list are valid, in no particular order. */
+#define EPS_PASS_IDS 0
+#define EPS_PASS_KEYS 1
+#define EPS_PASS_DENSE 2
+#define EPS_THR_RAW 0
+#define EPS_THR_DISTANCE 1
+int32_t eps_index_filter_pass(eps_index* h, const float* queries, int64_t nq, int32_t bits, int64_t row_lo, int64_t row_hi, int64_t cap, int32_t mode,
+                              int32_t thr_form, const void* thr, void* T_out, uint32_t* cnt_out, void* cand_out);
 int32_t eps_index_set_graph(eps_index* h, int64_t n, const int64_t* offsets, const int64_t* neighbors,
                             int64_t navigation_point);
 int32_t eps_index_graph_info(const eps_index* h, int64_t* n, int64_t* edges, int64_t* navigation_point);

@@ -66,6 +66,40 @@ def col_centre(X, sample=None):
     return (mean + z0).astype(F), F(max(chi - z0, z0 - clo))
 
 
+def _fma32(a, b, c):
+    """fl32(a * b + c) for float32 arrays, ONE rounding: the product of two fp32 values is exact in fp64; the fp64 sum is rounded to odd (TwoSum
+    gives the sign of what the fp64 addition lost), so that the final rounding to fp32 - 29 bits shorter - is the correct one"""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    bits = s.view(np.int64)
+    up = (err > 0) == (s > 0)     # the exact sum lies further from zero than s
+    odd = (err != 0) & np.isfinite(s) & ((bits & 1) == 0)
+    bits = np.where(odd, np.where(up, bits + 1, bits - 1), bits)   # (s = 0 with err != 0 cannot happen: then s would be err)
+    return bits.view(np.float64).astype(F)
+
+
+def lane_dot(A, B):
+    """sum_c A[r][c] * B[r][c] in fp32 in the ORDER quant_mirror_kernel / query_prep8_kernel use (mirror_build.hip): one wavefront per row, lane l
+    takes columns 4 l .. 4 l + 3 of every 256-column block in turn with sequential fmaf, then a 6-level xor tree (32, 16, .. 1) of fp32 additions"""
+    n, d = A.shape
+    dp = (d + 255) // 256 * 256
+    Ap, Bp = np.zeros((n, dp), F), np.zeros((n, dp), F)   # (columns beyond d are skipped on the device: fmaf(0, 0, acc) = acc)
+    Ap[:, :d], Bp[:, :d] = A, B
+    Ap, Bp = Ap.reshape(n, dp // 256, 64, 4), Bp.reshape(n, dp // 256, 64, 4)
+    acc = np.zeros((n, 64), F)
+    for k in range(dp // 256):
+        for e in range(4):
+            acc = _fma32(Ap[:, k, :, e], Bp[:, k, :, e], acc)
+    o = 32
+    while o:
+        acc = (acc + acc[:, np.arange(64) ^ o]).astype(F)
+        o >>= 1
+    return acc[:, 0]
+
+
 def mirror(X, metric, mu=None, step=None):
     if mu is None:
         mu, half = col_centre(X)
@@ -80,12 +114,14 @@ def mirror(X, metric, mu=None, step=None):
     xh = (step * xi.astype(F)).astype(F)
     s = F(2.0) if metric == 0 else F(1.0)
     u = s * step * step
-    x2c = (xc * xc).sum(1, dtype=F)
+    # R in the device's own summation order and a0 through the reciprocal, as quant_mirror_kernel forms them: acc0 is then the SAME integer the
+    # device stores (tests/test_gpu_mirror_pin.py asserts zero differences), not one that may sit on the other side of a ceil
+    x2c = lane_dot(xc, xc)
     if metric == 0:
         R = x2c
     else:
-        R = -(mu * xc).sum(1, dtype=F)
-    a0 = np.ceil(-R / u) + 1
+        R = -lane_dot(np.broadcast_to(mu, xc.shape), xc)
+    a0 = np.ceil((-R * (F(1.0) / u)).astype(F)) + 1
     # per ROW (r4): the two norms the Cauchy-Schwarz margin multiplies the query's with
     erow = (np.sqrt((res * res).sum(1, dtype=F)) * F(1.00001) + F(1.2e-7) * np.sqrt(x2c)).astype(F)   # + the rounding of x - mu
     hrow = (np.sqrt((xh * xh).sum(1, dtype=F)) * F(1.00001)).astype(F)

@@ -26,7 +26,7 @@ EXPORTS = [
     "eps_default_search_params", "eps_default_build_params", "eps_index_create", "eps_index_create_sharded", "eps_index_destroy",
     "eps_index_last_error", "eps_index_last_error_class", "eps_index_set_stream", "eps_index_synchronize", "eps_index_attach_rows",
     "eps_index_append_rows", "eps_index_attach_shard_rows", "eps_index_clone_rows", "eps_index_row_count", "eps_index_load_table", "eps_index_set_id_map", "eps_index_set_deleted",
-    "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
+    "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
     "eps_index_get_graph", "eps_index_save_graph", "eps_index_load_graph", "eps_index_search",
     "eps_index_last_stats", "eps_index_kernel_times", "eps_normalize_rows", "eps_merge_topk", "eps_merge_topk_packed", "eps_set_tuning",
     "eps_exchange_unique_id", "eps_exchange_create", "eps_exchange_allgather_merge", "eps_exchange_times", "eps_exchange_info", "eps_exchange_last_error",
@@ -79,7 +79,8 @@ def sync_tuning():
 class _Synced:
     """The loaded library; calls that may consult a switch forward the environment first (see sync_tuning)."""
     _SYNC = frozenset(("eps_index_search", "eps_index_search_walk", "eps_index_build", "eps_index_knn_graph", "eps_index_link",
-                       "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph"))
+                       "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph",
+                       "eps_index_mirror_view", "eps_index_filter_pass"))
 
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
@@ -128,6 +129,18 @@ class SearchStats(C.Structure):
                 ("main_kernel_launches", C.c_int64), ("main_kernel_rows", C.c_int64),
                 ("main_kernel_queries", C.c_int64), ("main_kernel_bits", C.c_int64),
                 ("filter_ms_all", C.c_double), ("filter_rows_all", C.c_int64), ("i8_folded", C.c_int64), ("i8_declined", C.c_int64), ("one_pass", C.c_int64), ("i8_rotated", C.c_int64)]
+
+
+class MirrorView(C.Structure):
+    """eps_mirror_view: scalars out, host buffers in (None = not wanted)"""
+    _fields_ = [("n", C.c_int64), ("n_pad", C.c_int64), ("forced_rows", C.c_int64), ("extended_rows", C.c_int64), ("d_pad", C.c_int32),
+                ("usable", C.c_int32), ("rot", C.c_int32), ("rot_w", C.c_int32), ("fold", C.c_int32), ("version", C.c_int32),
+                ("step", C.c_float), ("slack", C.c_float)] + [(name, C.c_void_p) for name in (
+                    "x", "acc0", "acc0b", "erow", "hrow", "mu", "sp", "scal", "scalf", "qmax", "xn", "start", "q", "qstat")]
+
+
+PASS_IDS, PASS_KEYS, PASS_DENSE = 0, 1, 2
+THR_RAW, THR_DISTANCE = 0, 1
 
 
 class EpsillaError(RuntimeError):
@@ -183,6 +196,8 @@ def load():
     L.eps_index_build.argtypes = [vp, i64, C.POINTER(BuildParams)]
     L.eps_index_knn_graph.argtypes = [vp, i64, C.POINTER(BuildParams), vp]
     L.eps_index_link.argtypes = [vp, i64, vp, i64, C.POINTER(BuildParams), vp, vp, C.POINTER(i64)]
+    L.eps_index_mirror_view.argtypes = [vp, i32, vp, i64, C.POINTER(MirrorView)]
+    L.eps_index_filter_pass.argtypes = [vp, vp, i64, i32, i64, i64, i64, i32, i32, vp, vp, vp, vp]
     L.eps_index_set_graph.argtypes = [vp, i64, vp, vp, i64]
     L.eps_index_graph_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.eps_index_get_graph.argtypes = [vp, vp, vp]

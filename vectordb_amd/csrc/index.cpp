@@ -1110,6 +1110,29 @@ int32_t eps_index_link(eps_index* h, int64_t n, const int64_t* knn, int64_t navi
     return map_exception(ix);
   }
 }
+int32_t eps_index_mirror_view(eps_index* h, int32_t bits, const float* queries, int64_t nq, eps_mirror_view* view) {
+  if (!h || !view) return EPS_USER_ERROR;
+  Index* ix = dynamic_cast<Index*>(IX(h));
+  if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, "mirror_view: single-device indices only", EPS_ERRCLASS_OTHER);
+  try {
+    if (hipSetDevice(ix->device_) != hipSuccess) return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");
+    return eps::flat_mirror_view(*ix, bits, queries, nq, view);
+  } catch (...) {
+    return map_exception(ix);
+  }
+}
+int32_t eps_index_filter_pass(eps_index* h, const float* queries, int64_t nq, int32_t bits, int64_t row_lo, int64_t row_hi, int64_t cap, int32_t mode,
+                              int32_t thr_form, const void* thr, void* T_out, uint32_t* cnt_out, void* cand_out) {
+  if (!h) return EPS_USER_ERROR;
+  Index* ix = dynamic_cast<Index*>(IX(h));
+  if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, "filter_pass: single-device indices only", EPS_ERRCLASS_OTHER);
+  try {
+    if (hipSetDevice(ix->device_) != hipSuccess) return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");
+    return eps::flat_filter_pass(*ix, queries, nq, bits, row_lo, row_hi, cap, mode, thr_form, thr, T_out, cnt_out, cand_out);
+  } catch (...) {
+    return map_exception(ix);
+  }
+}
 int32_t eps_index_load_table(eps_index* h, const char* path, const eps_table_layout* layout, int64_t* n_out) {
   if (!h) return EPS_USER_ERROR;
   Index* ix = dynamic_cast<Index*>(IX(h));

@@ -278,6 +278,10 @@ int32_t flat_mfma_search(Index& ix, const float* dq, int64_t nq, int k, u64* run
 int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool approx, int cap_scale = 1, int bits = 16,
                                bool auto_bits = false);  // <= 2048 queries
 bool flat_mfma_profitable(const Index& ix, int64_t nq, int k);  // AUTO heuristic
+// stage-level entries of the flat matrix engine (eps_index_mirror_view / eps_index_filter_pass): host arrays, no side effects a search could see
+int32_t flat_mirror_view(Index& ix, int bits, const float* queries, int64_t nq, eps_mirror_view* v);
+int32_t flat_filter_pass(Index& ix, const float* queries, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
+                         void* T_out, u32* cnt_out, void* cand_out);
 int32_t quant8_view(Index& ix, Quant8View* v);
 void quant8_queries(Index& ix, const Quant8View& v, const float* dq, int64_t nq, signed char* q8, float* qstat);
 void half_mirror_free(HalfMirror* m);

@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -683,6 +684,174 @@ int32_t flat_mfma_search(Index& ix, const float* dq, int64_t nq, int k, u64* run
     const int32_t rc = flat_mfma_search_slice(ix, dq + q0 * ix.dim_, std::min(slice, nq - q0), k, run_keys + q0 * k, approx, 1, bits, auto_bits);
     if (rc != EPS_OK) return rc;
   }
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ stages on their own (tests)
+// eps_index_mirror_view / eps_index_filter_pass (include/epsilla_gfx950.h): what the build and the preparation kernels store, and what ONE
+// filter launch lets through, handed to a test that compares them with an fp64 reference.  Both run the chain's own steps (plan_chain,
+// prepare_queries, filter_args, launch_filter) and leave nothing behind that a later search could see.
+namespace {
+// the call's statistics and the one-pass search's "clean state" as a probe must leave them
+struct ProbeGuard {
+  Index& ix;
+  eps_search_stats keep;
+  explicit ProbeGuard(Index& i) : ix(i), keep(i.stats_) {}
+  ~ProbeGuard() {
+    ix.stats_ = keep;
+    if (ix.mirror_) ix.mirror_->s8_clean_cnt = nullptr;   // (a probe writes the counters the one-pass form keeps its own in: its next call starts with the prep launch)
+  }
+};
+u64 host_key(float dist) {   // make_key(dist, 0) on the host
+  dist += 0.0f;
+  u32 u;
+  std::memcpy(&u, &dist, 4);
+  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
+  return (u64)u << 32;
+}
+int32_t upload_queries(Index& ix, const float* hq, int64_t nq, DevBuf* dq) {
+  if (!dq->reserve((size_t)nq * ix.dim_ * 4)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "out of device memory (queries)");
+  const hipError_t er = hipMemcpyAsync(dq->p, hq, (size_t)nq * ix.dim_ * 4, hipMemcpyHostToDevice, ix.stream_);
+  return er == hipSuccess ? EPS_OK : ix.hip_fail(er, "memcpy (queries)");
+}
+int32_t ensure_probe_mirror(Index& ix, bool i8) {
+  if (ix.n_rows_ <= 0) return ix.fail(EPS_USER_ERROR, "no rows attached");
+  return i8 ? ensure_mirror8(ix) : ensure_mirror(ix);
+}
+}  // namespace
+
+int32_t flat_mirror_view(Index& ix, int bits, const float* hq, int64_t nq, eps_mirror_view* v) {
+  if (bits != 8 && bits != 16) return ix.fail(EPS_USER_ERROR, "mirror_view: bits must be 8 or 16");
+  if (nq < 0 || nq > 2048 || (nq > 0 && !hq)) return ix.fail(EPS_USER_ERROR, "mirror_view: 0 .. 2048 host queries");
+  const bool i8 = bits == 8;
+  int32_t rc = ensure_probe_mirror(ix, i8);
+  if (rc != EPS_OK) return rc;
+  HalfMirror& m = *ix.mirror_;
+  hipStream_t s = ix.stream_;
+  v->n = i8 ? m.n8 : m.n;
+  v->n_pad = i8 ? m.n_pad8 : m.n_pad;
+  v->forced_rows = i8 ? m.forced_rows8 : 0;
+  v->extended_rows = i8 ? m.extended_rows8 : m.extended_rows;
+  v->d_pad = i8 ? m.d_pad8 : m.d_pad;
+  v->usable = i8 ? (m.i8_ok ? 1 : 0) : (m.fp16_range_ok ? 1 : 0);
+  v->rot = i8 && m.rot8 ? 1 : 0;
+  v->rot_w = i8 ? m.rot_w8 : 0;
+  v->fold = i8 && m.fold8 ? 1 : 0;
+  v->version = 0;
+  v->step = i8 ? m.step8 : 0.f;
+  v->slack = rerank_slack(ix.dim_);
+  if (!v->usable) return EPS_OK;   // (8-bit: the table does not fit one grid, its row buffers were given back; fp16: values beyond its range - no search reads it)
+  hipError_t er = hipSuccess;
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    if (dst && src && er == hipSuccess) er = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
+  };
+  const size_t rows = (size_t)v->n_pad, dp = (size_t)v->d_pad;
+  if (i8) {
+    get(v->x, m.x8.p, rows * dp);
+    get(v->acc0, m.acc0.p, rows * 4);
+    get(v->erow, m.erow.p, rows * 4);
+    get(v->hrow, m.hrow.p, rows * 4);
+    get(v->mu, m.mu8.p, dp * 4);
+    if (m.rot8) get(v->sp, m.sp8.p, dp * 4);
+    get(v->scal, m.scal8.p, 32);
+    get(v->scalf, m.scal8f.p, 32);
+  } else {
+    get(v->x, m.xh.p, rows * dp * 2);
+    get(v->xn, m.xn.p, rows * 4);
+    get(v->start, ix.metric_ == 0 ? m.xn_s.p : m.zeros_s.p, rows * 4);   // (what filter_args hands the kernel as start values)
+    get(v->scal, m.scal.p, 16);
+  }
+  if (er != hipSuccess) return ix.hip_fail(er, "mirror_view: copy");
+  if (nq > 0) {
+    ProbeGuard guard(ix);
+    DevBuf dq;
+    rc = upload_queries(ix, hq, nq, &dq);
+    Chain c;
+    if (rc == EPS_OK) rc = plan_chain(ix, m, dq.as<float>(), nq, 1, nullptr, false, 1, i8, ix.n_rows_, &c);
+    if (rc == EPS_OK) rc = prepare_queries(ix, m, c);
+    if (rc != EPS_OK) return rc;
+    v->version = c.version;
+    get(v->q, i8 ? m.q8.p : m.qh.p, (size_t)nq * dp * (i8 ? 1 : 2));
+    get(v->qstat, m.qstat.p, (size_t)nq * 16);
+    if (i8 && c.fold) {
+      get(v->acc0b, m.acc0b.p, rows * 4);
+      get(v->qmax, m.qmax.p, 8);
+    }
+    if (er == hipSuccess) er = hipStreamSynchronize(s);   // (before the queries' device copy goes)
+    if (er != hipSuccess) return ix.hip_fail(er, "mirror_view: queries");
+  }
+  er = hipStreamSynchronize(s);
+  return er == hipSuccess ? EPS_OK : ix.hip_fail(er, "mirror_view");
+}
+
+int32_t flat_filter_pass(Index& ix, const float* hq, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
+                         void* T_out, u32* cnt_out, void* cand_out) {
+  if (bits != 8 && bits != 16) return ix.fail(EPS_USER_ERROR, "filter_pass: bits must be 8 or 16");
+  if (nq < 1 || nq > 2048 || !hq) return ix.fail(EPS_USER_ERROR, "filter_pass: 1 .. 2048 host queries");
+  if (mode < EPS_PASS_IDS || mode > EPS_PASS_DENSE || thr_form < EPS_THR_RAW || thr_form > EPS_THR_DISTANCE) return ix.fail(EPS_USER_ERROR, "filter_pass: unknown mode");
+  if (!cnt_out || !cand_out || (!thr && mode != EPS_PASS_DENSE)) return ix.fail(EPS_USER_ERROR, "filter_pass: null argument");
+  const bool i8 = bits == 8;
+  int32_t rc = ensure_probe_mirror(ix, i8);
+  if (rc != EPS_OK) return rc;
+  HalfMirror& m = *ix.mirror_;
+  const int64_t n = ix.n_rows_;
+  if (i8 ? !m.i8_ok : !m.fp16_range_ok) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, "filter_pass: the table has no usable mirror of this width");
+  if (lo < 0 || lo >= hi || hi > n || lo % BM3 != 0) return ix.fail(EPS_USER_ERROR, "filter_pass: rows [lo, hi) must lie in the table, lo on a multiple of 256");
+  if (cap < 1 || cap > ((int64_t)1 << 30) || (size_t)nq * (size_t)cap * 8 > ((size_t)8 << 30)) return ix.fail(EPS_USER_ERROR, "filter_pass: candidate cap out of range");
+  if (mode == EPS_PASS_DENSE && cap < hi - lo) return ix.fail(EPS_USER_ERROR, "filter_pass: the dense form needs one slot per row of the range");
+  hipStream_t s = ix.stream_;
+  ProbeGuard guard(ix);
+  const bool approx = mode != EPS_PASS_IDS;   // (the chain launches the key and the dense forms in its approx mode, on the unfolded start values)
+  DevBuf dq, keys;
+  rc = upload_queries(ix, hq, nq, &dq);
+  Chain c;
+  if (rc == EPS_OK) rc = plan_chain(ix, m, dq.as<float>(), nq, 1, nullptr, approx, 1, i8, n, &c);
+  if (rc != EPS_OK) return rc;
+  if (mode == EPS_PASS_DENSE && c.version < 7) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, "filter_pass: the dense form exists for the v7 kernel's shapes only");
+  c.cap = (int)cap;
+  if (!m.cand.reserve((size_t)nq * (size_t)cap * 8) || !keys.reserve((size_t)nq * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "filter_pass: out of device memory");
+  rc = prepare_queries(ix, m, c);
+  if (rc != EPS_OK) return rc;
+  ensure_filter_kernels(ix, m);
+  // thresholds: the padding entries and - from distances - every query's T by the chain's own kernels; raw ones are used as they are
+  hipError_t er = hipSuccess;
+  const int pad_only = thr_form == EPS_THR_DISTANCE && mode != EPS_PASS_DENSE ? 0 : 1;
+  if (!pad_only) {
+    std::vector<u64> hk((size_t)nq);
+    for (int64_t j = 0; j < nq; ++j) hk[(size_t)j] = host_key(static_cast<const float*>(thr)[j]);
+    er = hipMemcpyAsync(keys.p, hk.data(), (size_t)nq * 8, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);
+    if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: thresholds");
+  }
+  const dim3 tgrid((unsigned)((c.b_pad + 255) / 256));
+  if (i8)
+    hipLaunchKernelGGL(threshold8_kernel, tgrid, dim3(256), 0, s, keys.as<u64>(), 1, nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, c.u8, m.T.as<int>(), c.c.cnt,
+                       m.gsync.as<u32>(), c.slack, approx ? 1 : 0, pad_only);
+  else
+    hipLaunchKernelGGL(threshold_kernel, tgrid, dim3(256), 0, s, keys.as<u64>(), 1, nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, m.T.as<float>(), c.c.cnt,
+                       m.gsync.as<u32>(), c.slack, approx ? 1 : 0, pad_only);
+  if (pad_only) {
+    if (mode != EPS_PASS_DENSE) er = hipMemcpyAsync(m.T.p, thr, (size_t)nq * 4, hipMemcpyHostToDevice, s);
+    else er = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.T.p), 0x7F800000, (size_t)nq, s);   // (the seed pass's start state; the dense form reads no threshold)
+    if (er == hipSuccess) er = hipMemsetAsync(c.c.cnt, 0, (size_t)nq * 4, s);
+  }
+  if (er == hipSuccess) er = hipMemsetAsync(m.gsync.p, 0, 1024, s);
+  if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: start state");
+  FilterArgs fa = filter_args(ix, m, c);
+  fa.tile0 = lo / BM3;
+  fa.ntiles = (hi + BM3 - 1) / BM3 - fa.tile0;
+  fa.row_hi = hi;
+  fa.dense = mode == EPS_PASS_DENSE ? 1 : 0;
+  launch_filter(m, c, fa, s);
+  er = hipGetLastError();
+  if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: launch");
+  if (T_out) er = hipMemcpyAsync(T_out, m.T.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess && mode != EPS_PASS_DENSE) er = hipMemcpyAsync(cnt_out, c.c.cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(cand_out, m.cand.p, (size_t)nq * (size_t)cap * (approx ? 8 : 4), hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return ix.hip_fail(er, "filter_pass");
+  if (mode == EPS_PASS_DENSE)
+    for (int64_t j = 0; j < nq; ++j) cnt_out[j] = (u32)(hi - lo);
   return EPS_OK;
 }
 

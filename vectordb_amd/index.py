@@ -250,6 +250,69 @@ class GpuIndex:
         self._check(self.L.eps_index_link(self.h, n, _ptr(knn), int(nav), C.byref(bp), _ptr(out), _ptr(deg), C.byref(nav_out)))
         return out, deg, int(nav_out.value)
 
+    def mirror_view(self, bits, queries=None):
+        """eps_index_mirror_view: what the kernels of the flat matrix engine read, as a dict of numpy arrays - the mirror of width `bits`
+        (8 | 16; built or extended as a search would) and `queries` prepared as the staged chain prepares them.  Per-row arrays hold n_pad
+        rows.  8-bit: x8 [n_pad][d_pad8] int8, acc0, erow, hrow, mu8, sp8 (rotated frame), scal8, scal8f, q8, qstat, and - when the table
+        folds per-row margins - acc0b, qmax; fp16: xh, xn, start, scal, qh, qstat.  Scalars under their own names."""
+        q = None if queries is None else np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = 0 if q is None else len(q)
+        v = lib.MirrorView()
+        self._check(self.L.eps_index_mirror_view(self.h, int(bits), None, 0, C.byref(v)))   # the sizes (no buffer, no query)
+        out = {name: getattr(v, name) for name in ("n", "n_pad", "forced_rows", "extended_rows", "d_pad", "usable", "rot", "rot_w", "fold", "step", "slack")}
+        out["bits"], out["metric"], out["dim"] = int(bits), self.metric, self.dim
+        if not v.usable:
+            return out
+        n_pad, d_pad = v.n_pad, v.d_pad
+        if bits == 8:
+            bufs = dict(x=("x8", (n_pad, d_pad), np.int8), acc0=("acc0", (n_pad,), np.int32), erow=("erow", (n_pad,), np.float32),
+                        hrow=("hrow", (n_pad,), np.float32), mu=("mu8", (d_pad,), np.float32), scal=("scal8", (8,), np.float32),
+                        scalf=("scal8f", (8,), np.float32))
+            if v.rot:
+                bufs["sp"] = ("sp8", (d_pad,), np.int32)
+            if nq:
+                bufs.update(q=("q8", (nq, d_pad), np.int8), qstat=("qstat", (nq, 4), np.float32))
+                if v.fold:
+                    bufs.update(acc0b=("acc0b", (n_pad,), np.int32), qmax=("qmax", (2,), np.uint32))
+        else:
+            bufs = dict(x=("xh", (n_pad, d_pad), np.float16), xn=("xn", (n_pad,), np.float32), start=("start", (n_pad,), np.float32),
+                        scal=("scal", (4,), np.float32))
+            if nq:
+                bufs.update(q=("qh", (nq, d_pad), np.float16), qstat=("qstat", (nq, 4), np.float32))
+        for field, (name, shape, dt) in bufs.items():
+            out[name] = np.zeros(shape, dt)
+            setattr(v, field, out[name].ctypes.data)
+        self._check(self.L.eps_index_mirror_view(self.h, int(bits), _ptr(q), nq, C.byref(v)))
+        out["version"] = v.version
+        return out
+
+    def filter_pass(self, queries, bits, lo, hi, cap, thr, mode="ids", thr_is_distance=False):
+        """eps_index_filter_pass: ONE launch of the filter kernel over rows [lo, hi) with imposed thresholds `thr` [nq] (raw: int32 for
+        bits = 8, float32 for 16; or distances, turned into T by the device).  Returns (cnt [nq] rows that passed, lists, T [nq] used):
+        lists = per query the min(cnt, cap) row ids (mode "ids"), or (distances, rows) of the approximate keys ("keys", "dense": slot
+        = row - lo, every row of the range)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = len(q)
+        m = {"ids": lib.PASS_IDS, "keys": lib.PASS_KEYS, "dense": lib.PASS_DENSE}[mode]
+        tdt = np.float32 if (thr_is_distance or bits == 16) else np.int32
+        t_in = None if thr is None else np.ascontiguousarray(np.broadcast_to(np.asarray(thr, tdt), (nq,)))
+        T = np.zeros(nq, np.int32 if bits == 8 else np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        cand = np.zeros((nq, int(cap)), np.uint32 if m == lib.PASS_IDS else np.uint64)
+        self._check(self.L.eps_index_filter_pass(self.h, _ptr(q), nq, int(bits), int(lo), int(hi), int(cap), m,
+                                                 lib.THR_DISTANCE if thr_is_distance else lib.THR_RAW, _ptr(t_in), _ptr(T), _ptr(cnt), _ptr(cand)))
+        cnt = cnt.astype(np.int64)
+        lists = []
+        for j in range(nq):
+            c = cand[j, :min(int(cnt[j]), int(cap))]
+            if m == lib.PASS_IDS:
+                lists.append(c.astype(np.int64))
+            else:   # key = order-preserving image of the fp32 distance << 32 | row (device_common.hpp, make_key); ~0 = a NaN key of the dense form
+                o = (c >> np.uint64(32)).astype(np.uint32)
+                u = np.where(o & np.uint32(0x80000000), o ^ np.uint32(0x80000000), ~o)
+                lists.append((u.view(np.float32), (c & np.uint64(0xFFFFFFFF)).astype(np.int64)))
+        return cnt, lists, T
+
     def select_edges(self, nodes, cands, depth=300, out_degree=50):
         """SyncPrune's sort + SelectEdge for given candidate lists (eps_index_select_edges); returns (ids [m][R] -1 padded, deg [m])"""
         nodes = np.ascontiguousarray(nodes, np.int64)
