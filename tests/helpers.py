@@ -9,7 +9,8 @@ def assert_topk_match(ids, dist, ref_ids, ref_dist, rtol=1e-4, atol=1e-6, what="
     """GPU top-k vs oracle top-k for ONE query.  Distances must agree to rtol (north_star: 1e-4 relative).
     IDs must be identical position by position, except inside groups of candidates whose oracle distances are
     closer than the fp32 summation-order noise (|d_i - d_j| <= 4e-6 * max(|d|, 1)): there the two sides may
-    order/choose differently, which the reference itself would do on another compiler."""
+    order/choose differently, which the reference itself would do on another compiler.
+    (A tolerance, for the comparisons with the oracle.  A test that wants a derived BOUND instead: exact_ref.check_topk / check_exact.)"""
     ids, ref_ids = np.asarray(ids), np.asarray(ref_ids)
     dist, ref_dist = np.asarray(dist, np.float64), np.asarray(ref_dist, np.float64)
     assert len(ids) == len(ref_ids), "%s: %d results vs %d expected" % (what, len(ids), len(ref_ids))

@@ -25,14 +25,7 @@ def amd():
     return vectordb_amd
 
 
-def unit(X):
-    return (X / np.linalg.norm(X, axis=1, keepdims=True)).astype(F)
-
-
-def embedding_like(rng, n, d):
-    scale = np.ones(d, F)
-    scale[:8] = 4.0
-    return unit(rng.standard_normal((n, d)).astype(F) * scale)
+from exact_ref import embedding_like, unit  # noqa: E402  (the tables both fp64 references are fed with)
 
 
 def forced_row_table(rng, n, d):

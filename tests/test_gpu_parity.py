@@ -308,6 +308,28 @@ def test_flat_large_properties(amd):
         assert_topk_match((ids_h[qi] - 3) // 8, dist_h[qi], o, ex[o])
         assert np.all((ids_h[qi] - 3) % 8 == 0)
     ix.close()
+    # metrics 1 and 2 at the same size, on the same rows (normalised for COSINE), under the contract of tests/exact_ref.py: every distance
+    # within the order-free AND the tree bound of its row's fp64 distance, (distance, id) pairs in order, membership outside the band
+    import exact_ref as xr
+    sample = np.arange(0, nq, 7)
+    for metric in (1, 2):
+        Xm, Qm = X, Qd
+        if metric == 1:
+            Xm = X / X.norm(dim=1, keepdim=True)
+            Qm = Qd / Qd.norm(dim=1, keepdim=True)
+        ix = amd.GpuIndex(d, metric).use_torch_stream()
+        ix.attach_rows(Xm)
+        ix.set_id_map(3, 8)
+        ix.search(Qm, k, out=(ids, dist, cnt), mode=amd.MODE_FLAT, flat_engine=amd.FLAT_STREAM)
+        ix.synchronize()
+        Xh, Qh = Xm.cpu().numpy(), Qm.cpu().numpy()
+        ids_h, dist_h, cnt_h = ids.cpu().numpy(), dist.cpu().numpy(), cnt.cpu().numpy()
+        assert np.all((ids_h - 3) % 8 == 0)
+        ref = xr.Ref(Xh, Qh[sample], metric)
+        xr.assert_cap(ref, k, what="large m%d" % metric)
+        for bound in ("free", "tree"):
+            xr.check_topk((ids_h[sample] - 3) // 8, dist_h[sample], cnt_h[sample], Xh, None, metric, k, ref=ref, bound=bound, what="large m%d" % metric)
+        ix.close()
 
 
 def test_merge_topk(amd):

@@ -57,7 +57,10 @@ __host__ __device__ inline FilterSpec no_filter() { return FilterSpec{nullptr, n
 
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-// fp32 -> u32 preserving order (NaN sorts last, -0 is folded into +0 by the callers' `+ 0.0f`)
+// fp32 -> u32 preserving order of everything that is a number (-0 is folded into +0 by the callers' `+ 0.0f`).  A NaN's word would land
+// above +inf with its sign bit clear and BELOW every number with it set - and DOT_PRODUCT's `-acc` sets it - so make_key gives every NaN ONE
+// ordinal of its own, ORD_NAN: above +inf, below KEY_EMPTY's high word.  "NaN sorts last" is make_key's promise, not f2ord's.
+constexpr u32 ORD_NAN = 0xFFC00000u;   // (ord2f(ORD_NAN) is the canonical quiet NaN: a NaN comes back as a NaN)
 __device__ __forceinline__ u32 f2ord(float f) {
   u32 u = __float_as_uint(f);
   return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
@@ -66,7 +69,10 @@ __device__ __forceinline__ float ord2f(u32 o) {
   u32 u = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
   return __uint_as_float(u);
 }
-__device__ __forceinline__ u64 make_key(float dist, u32 id) { return ((u64)f2ord(dist + 0.0f) << 32) | (u64)id; }
+__device__ __forceinline__ u64 make_key(float dist, u32 id) {
+  const float d = dist + 0.0f;
+  return ((u64)(d != d ? ORD_NAN : f2ord(d)) << 32) | (u64)id;
+}
 __device__ __forceinline__ float key_dist(u64 k) { return ord2f((u32)(k >> 32)); }
 __host__ __device__ __forceinline__ u32 key_id(u64 k) { return (u32)k; }
 

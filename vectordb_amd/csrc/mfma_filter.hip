@@ -704,6 +704,7 @@ struct ProbeGuard {
 };
 u64 host_key(float dist) {   // make_key(dist, 0) on the host
   dist += 0.0f;
+  if (dist != dist) return (u64)ORD_NAN << 32;   // (one ordinal for every NaN, as make_key)
   u32 u;
   std::memcpy(&u, &dist, 4);
   u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
