@@ -293,6 +293,52 @@ struct Compiler {
 };
 }  // namespace
 
+// dev.mu held.  What a device call of an executor finds in HBM before it runs: the rows appended since the last call, the index a
+// rebuild left waiting for this segment, and this executor's graph.  Throws like Search().
+static void SyncRowsAndGraph(DeviceField& dev, VecSearchExecutor& ex, vectordb::engine::TableSegmentMVP* table_segment) {
+  auto fail = [&](const char* what) { throw std::runtime_error(std::string("gfx950 executor: ") + what + ": " + eps_index_last_error(dev.h)); };
+  // rows [0, record_number_) are immutable once written (SURVEY §8b "Ownership"): upload only the new tail
+  const int64_t total_vector = table_segment->record_number_;
+  if (total_vector > dev.attached) {
+    const float* base = std::get<DenseVectorColumnDataContainer>(ex.vector_column_);
+    const int32_t rc = dev.attached == 0 ? eps_index_attach_rows(dev.h, base, total_vector)
+                                         : eps_index_append_rows(dev.h, base + dev.attached * ex.dimension_, total_vector - dev.attached);
+    if (rc != EPS_OK) fail("row upload");
+    dev.attached = total_vector;
+  }
+  {
+    const std::string aerr = AdoptPendingBuild(dev, ex.ann_index_->OwnerKey(), ex.dimension_);
+    if (!aerr.empty()) throw std::runtime_error(aerr);
+  }
+  // (an executor of the segment a rebuild just replaced finishes on the new graph: uploading its old CSR again would only be undone by
+  // the next search of the new segment)
+  if (!dev.sharded && ex.ann_index_->OwnerKey() != dev.retired_owner &&
+      (dev.graph_owner != ex.ann_index_->OwnerKey() || dev.graph_n != ex.total_indexed_vector_)) {
+    if (eps_index_set_graph(dev.h, ex.total_indexed_vector_, ex.offset_table_, ex.neighbor_list_, ex.start_search_point_) != EPS_OK) fail("graph upload");
+    dev.graph_owner = ex.ann_index_->OwnerKey();
+    dev.retired_owner = nullptr;   // (another segment's graph is in HBM now: nobody runs "on the graph that replaced mine" any more)
+    dev.graph_n = ex.total_indexed_vector_;
+  }
+}
+
+// dev.mu held.  The call's predicate: the compiled program (empty = none) over the segment's attribute rows, and the deleted bitset.
+static void SyncPredicate(DeviceField& dev, vectordb::engine::TableSegmentMVP* table_segment, const std::vector<eps_filter_op>& program) {
+  auto fail = [&](const char* what) { throw std::runtime_error(std::string("gfx950 executor: ") + what + ": " + eps_index_last_error(dev.h)); };
+  ConcurrentBitset& deleted = *(table_segment->deleted_);
+  if (eps_index_set_int_filter(dev.h, nullptr, 0, 0, EPS_OP_NONE, 0) != EPS_OK) fail("filter reset");
+  if (!program.empty()) {
+    // the attribute rows are handed over as they are: TableSegmentMVP::attribute_table_, primitive_offset_ bytes per row
+    // (append-only: an update of the reference's table is delete + insert, table_segment_mvp.cpp:476-587; the device mirror is per
+    // table segment, so a dropped-and-recreated table never meets a cached copy)
+    if (eps_index_set_filter_program_ex(dev.h, program.data(), (int32_t)program.size(), table_segment->attribute_table_,
+                                        table_segment->primitive_offset_, table_segment->record_number_, EPS_FILTER_ROWS_APPEND_ONLY) != EPS_OK)
+      fail("filter program upload");
+  } else if (eps_index_set_filter_program(dev.h, nullptr, 0, nullptr, 0, 0) != EPS_OK) {
+    fail("filter reset");
+  }
+  if (eps_index_set_deleted(dev.h, deleted.data(), (int64_t)deleted.size()) != EPS_OK) fail("deleted upload");
+}
+
 VecSearchExecutor::VecSearchExecutor(const int64_t dimension, const int64_t start_search_point,
                                      std::shared_ptr<ANNGraphSegment> ann_index, int64_t* offset_table,
                                      int64_t* neighbor_list,
@@ -353,28 +399,8 @@ Status VecSearchExecutor::Search(const VectorPtr query_data, vectordb::engine::T
     throw std::runtime_error(std::string("gfx950 executor: ") + what + ": " + eps_index_last_error(dev.h));
   };
 
-  // rows [0, record_number_) are immutable once written (SURVEY §8b "Ownership"): upload only the new tail
   const int64_t total_vector = table_segment->record_number_;
-  if (total_vector > dev.attached) {
-    const float* base = std::get<DenseVectorColumnDataContainer>(vector_column_);
-    const int32_t rc = dev.attached == 0 ? eps_index_attach_rows(dev.h, base, total_vector)
-                                         : eps_index_append_rows(dev.h, base + dev.attached * dimension_, total_vector - dev.attached);
-    if (rc != EPS_OK) return fail("row upload");
-    dev.attached = total_vector;
-  }
-  {
-    const std::string aerr = AdoptPendingBuild(dev, ann_index_->OwnerKey(), dimension_);
-    if (!aerr.empty()) throw std::runtime_error(aerr);
-  }
-  // (an executor of the segment a rebuild just replaced finishes on the new graph: uploading its old CSR again would only be undone by
-  // the next search of the new segment)
-  if (!dev.sharded && ann_index_->OwnerKey() != dev.retired_owner && (dev.graph_owner != ann_index_->OwnerKey() || dev.graph_n != total_indexed_vector_)) {
-    if (eps_index_set_graph(dev.h, total_indexed_vector_, offset_table_, neighbor_list_, start_search_point_) != EPS_OK)
-      return fail("graph upload");
-    dev.graph_owner = ann_index_->OwnerKey();
-    dev.retired_owner = nullptr;   // (another segment's graph is in HBM now: nobody runs "on the graph that replaced mine" any more)
-    dev.graph_n = total_indexed_vector_;
-  }
+  SyncRowsAndGraph(dev, *this, table_segment);
 
   // ---- filter lowering
   ConcurrentBitset& deleted = *(table_segment->deleted_);
@@ -386,18 +412,7 @@ Status VecSearchExecutor::Search(const VectorPtr query_data, vectordb::engine::T
     c.Logical((size_t)root, true);
     if (c.host_only || c.out.size() > 64) host_filter = true; else program.swap(c.out);
   }
-  if (eps_index_set_int_filter(dev.h, nullptr, 0, 0, EPS_OP_NONE, 0) != EPS_OK) return fail("filter reset");
-  if (!program.empty()) {
-    // the attribute rows are handed over as they are: TableSegmentMVP::attribute_table_, primitive_offset_ bytes per row
-    // (append-only: an update of the reference's table is delete + insert, table_segment_mvp.cpp:476-587; the device mirror is per
-    // table segment, so a dropped-and-recreated table never meets a cached copy)
-    if (eps_index_set_filter_program_ex(dev.h, program.data(), (int32_t)program.size(), table_segment->attribute_table_,
-                                        table_segment->primitive_offset_, total_vector, EPS_FILTER_ROWS_APPEND_ONLY) != EPS_OK)
-      return fail("filter program upload");
-  } else if (eps_index_set_filter_program(dev.h, nullptr, 0, nullptr, 0, 0) != EPS_OK) {
-    return fail("filter reset");
-  }
-  if (eps_index_set_deleted(dev.h, deleted.data(), (int64_t)deleted.size()) != EPS_OK) return fail("deleted upload");
+  SyncPredicate(dev, table_segment, program);
 
   eps_search_params p;
   eps_default_search_params(&p);
@@ -798,10 +813,46 @@ Status VecSearchExecutor::SearchByAttribute(meta::TableSchema& table_schema, vec
     for (auto& h : hits)
       if (!offer(h.second)) break;
   }
-  if (!used_geo)
-    for (int64_t id = 0; id < total_vector; ++id)
-      if (!offer(id)) break;
+  if (used_geo) return Status::OK();
+  if (SelectOnDevice(table_segment, skip, limit, filter_nodes, result_size)) return Status::OK();
+  for (int64_t id = 0; id < total_vector; ++id)
+    if (!offer(id)) break;
   return Status::OK();
+}
+
+// Tables below this many rows keep the host loop of SearchByAttribute's full scan: see DESIGN.md ("Filter-only gets") for the measurement
+// behind it.  EPS_DROPIN_SELECT_MIN_ROWS overrides it (read on every call).
+constexpr int64_t kSelectMinRows = 2048;
+
+// The full-scan branch (:1016-1029) on the device: eps_index_select over the field's mirror, when the table is large enough, the mirror is
+// one device and the filter is empty / true or compiles to a device program.  false = not taken (nothing was touched): the host loop answers.
+// A device error throws, as in Search(): the two paths never stand in for each other on failure.
+bool VecSearchExecutor::SelectOnDevice(vectordb::engine::TableSegmentMVP* table_segment, size_t skip, int64_t limit,
+                                       std::vector<ExprNodePtr>& filter_nodes, int64_t& result_size) {
+  if (!dev_ || dev_->sharded) return false;
+  const int64_t total_vector = table_segment->record_number_;
+  int64_t min_rows = kSelectMinRows;
+  if (const char* e = getenv("EPS_DROPIN_SELECT_MIN_ROWS"))
+    if (*e) min_rows = atoll(e);
+  if (total_vector < min_rows || total_vector <= 0) return false;
+  const int root = static_cast<int>(filter_nodes.size()) - 1;
+  std::vector<eps_filter_op> program;
+  if (root >= 0 && !(filter_nodes[root]->node_type == NodeType::BoolConst && filter_nodes[root]->bool_value)) {
+    Compiler c{filter_nodes, table_segment};
+    c.Logical((size_t)root, false);   // (LogicalEvaluate(root, id): no distance, :1018)
+    if (c.host_only || c.out.size() > 64) return false;
+    program.swap(c.out);
+  }
+  DeviceField& dev = *dev_;
+  std::lock_guard<std::mutex> lk(dev.mu);
+  SyncRowsAndGraph(dev, *this, table_segment);
+  SyncPredicate(dev, table_segment, program);
+  int64_t count = 0;
+  const int64_t dskip = (int64_t)std::min<size_t>(skip, (size_t)total_vector);   // (no rank reaches total_vector)
+  if (eps_index_select(dev.h, dskip, limit, search_result_.data(), &count, nullptr) != EPS_OK)
+    throw std::runtime_error(std::string("gfx950 executor: select: ") + eps_index_last_error(dev.h));
+  result_size = count;
+  return true;
 }
 
 }  // namespace execution

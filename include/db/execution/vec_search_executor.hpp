@@ -92,6 +92,9 @@ class VecSearchExecutor {
   // executors that carry the same filter program into one device batch
   Status SearchBatched(const float* query, vectordb::engine::TableSegmentMVP* table_segment, size_t limit, int64_t& result_size,
                        const std::vector<eps_filter_op>* program);
+  // SearchByAttribute's full scan through eps_index_select; false = the host loop answers (small table, sharded or no mirror, host-only filter)
+  bool SelectOnDevice(vectordb::engine::TableSegmentMVP* table_segment, size_t skip, int64_t limit,
+                      std::vector<vectordb::query::expr::ExprNodePtr>& filter_nodes, int64_t& result_size);
   std::shared_ptr<DeviceField> dev_;
   int metric_ = 0;
 };

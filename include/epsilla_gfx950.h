@@ -21,6 +21,8 @@
  *                                   selection, SearchImpl (:518-715), BruteForceSearch (:717-768),
  *                                   PreFilterBruteForceSearch (:770-831), tail merge, post-filter; results are
  *                                   what the caller reads from search_result_ / distance_ (hpp:51-52)
+ *   eps_index_select                VecSearchExecutor::SearchByAttribute's full scan (.cpp:1016-1029): the visible rows in row
+ *                                   order, windowed by skip / limit
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -363,6 +365,17 @@ int32_t eps_index_search(eps_index* h, const float* queries, int64_t nq, int32_t
  * instead of O(N). */
 int32_t eps_index_search_walk(eps_index* h, const float* queries, int64_t nq, int32_t limit, int32_t cap, const eps_search_params* p,
                               int64_t* ids_out, float* dist_out, int32_t* counts_out);
+/* VecSearchExecutor::SearchByAttribute's full-scan branch (db/execution/vec_search_executor.cpp:1016-1029) - the path behind DBServer::Project,
+ * the client's `get` without a primary-key list: the rows of [0, eps_index_row_count) that are not deleted and pass the filter (whatever
+ * eps_index_set_deleted, eps_index_set_int_filter and eps_index_set_filter_program last installed; `@distance` reads as 0, as
+ * LogicalEvaluate(root, id) evaluates it there), in ascending row order; those of rank [skip, skip + limit) among them are written as
+ * ids_out[rank - skip] = row * stride + base (eps_index_set_id_map).  *count_out = clamp(total - skip, 0, limit) ids were written;
+ * *total_out (may be NULL) = the visible rows of the whole table, a `count where` for free.  ids_out [limit], count_out [1], total_out [1]:
+ * host or device, all the same kind - device: asynchronous on the index's stream; host: the call synchronises, as eps_index_search does.
+ * limit = 0 or an empty table: count 0.  Negative skip / limit: EPS_USER_ERROR.  A sharded handle: EPS_DB_UNSUPPORTED_ERROR.  Nothing a later
+ * search can observe changes (filters, statistics, engine choices).  Three launches (csrc/select.hip): verdict bitset + block counts, scan
+ * of the counts, scatter of the window - the reference's loop is serial over all rows (`TODO: leverage multithread to accelerate`, :945). */
+int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

@@ -883,6 +883,68 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
   return EPS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ select
+// SearchByAttribute's full-scan branch (vec_search_executor.cpp:1016-1029).  Touches nothing a search reads: no statistics, no event of the
+// kernel ring, no engine state - only scratch of its own.
+int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out) {
+  if (skip < 0 || limit < 0) return fail(EPS_USER_ERROR, "select: skip and limit must be >= 0");
+  if (!count_out || (limit > 0 && n_rows_ > 0 && !ids_out)) return fail(EPS_USER_ERROR, "select: null buffer");
+  HIP_TRY(hipSetDevice(device_));
+  if (d_deleted_ && deleted_bytes_ < (n_rows_ + 7) / 8)
+    return fail(EPS_USER_ERROR, "select: the deleted bitset is shorter than the table (rows were appended): call set_deleted again");
+  if (f_op_ && d_fcol_ && fcol_rows_ < n_rows_)
+    return fail(EPS_USER_ERROR, "select: the filter column is shorter than the table (rows were appended): call set_int_filter again");
+  if (prog_len_ > 0 && prog_rows_n_ < n_rows_)
+    return fail(EPS_USER_ERROR, "select: the filter program's attribute rows are shorter than the table (rows were appended): call set_filter_program again");
+  const int64_t n = n_rows_;
+  const bool out_dev = is_device_ptr(count_out);
+  if ((limit > 0 && n > 0 && out_dev != is_device_ptr(ids_out)) || (total_out && out_dev != is_device_ptr(total_out)))
+    return fail(EPS_USER_ERROR, "select: ids_out, count_out and total_out must all be host or all be device pointers");
+  if (n == 0) {   // an empty table: nothing to judge
+    if (out_dev) {
+      HIP_TRY(hipMemsetAsync(count_out, 0, sizeof(int64_t), stream_));
+      if (total_out) HIP_TRY(hipMemsetAsync(total_out, 0, sizeof(int64_t), stream_));
+    } else {
+      *count_out = 0;
+      if (total_out) *total_out = 0;
+    }
+    return EPS_OK;
+  }
+  SelectArgs a;
+  a.f = filter_spec();
+  a.f.prog_use_dist = 0;   // LogicalEvaluate(root, id): no distance (:1018)
+  a.n = n;
+  a.skip = std::min(skip, n);   // (no rank reaches n: the window's end cannot overflow)
+  a.limit = std::min(limit, n);
+  a.id_base = id_base_;
+  a.id_stride = id_stride_;
+  const int64_t nblocks = select_blocks(n);
+  const size_t counts_bytes = ((size_t)nblocks * sizeof(u32) + 7) & ~(size_t)7;
+  if (!sel_bits_.reserve((size_t)nblocks * (SEL_ROWS / 8)) || !sel_scan_.reserve(counts_bytes + (size_t)(nblocks + 1) * sizeof(int64_t)) ||
+      (!out_dev && !sel_out_.reserve((size_t)(2 + a.limit) * sizeof(int64_t))))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "select: out of device memory (scratch)");
+  a.bits = sel_bits_.as<u64>();
+  a.counts = sel_scan_.as<u32>();
+  a.offsets = reinterpret_cast<int64_t*>(sel_scan_.as<char>() + counts_bytes);
+  a.ids_out = out_dev ? ids_out : sel_out_.as<int64_t>() + 2;
+  a.count_out = out_dev ? count_out : sel_out_.as<int64_t>();
+  a.total_out = out_dev ? total_out : sel_out_.as<int64_t>() + 1;
+  launch_select(a, stream_);
+  HIP_TRY(hipGetLastError());
+  if (!out_dev) {   // count and total first: only the ids of the window cross PCIe, not `limit` slots
+    int64_t head[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(head, sel_out_.p, sizeof(head), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (head[0] > 0) {
+      HIP_TRY(hipMemcpyAsync(ids_out, a.ids_out, (size_t)head[0] * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+      HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    *count_out = head[0];
+    if (total_out) *total_out = head[1];
+  }
+  return EPS_OK;
+}
+
 int32_t Index::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   // event timings are read lazily: the caller may have left the work in flight
@@ -1155,6 +1217,16 @@ int32_t eps_index_load_graph(eps_index* h, const char* path) { GUARD(h, IX(h)->l
 int32_t eps_index_search(eps_index* h, const float* q, int64_t nq, int32_t k, const eps_search_params* p, int64_t* ids,
                          float* dist, int32_t* counts) {
   GUARD(h, IX(h)->search(q, nq, k, p, ids, dist, counts));
+}
+int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out) {
+  if (!h) return EPS_USER_ERROR;
+  Index* ix = dynamic_cast<Index*>(IX(h));
+  if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, "select: single-device indices only (a sharded table is not served)");
+  try {
+    return ix->select(skip, limit, ids_out, count_out, total_out);
+  } catch (...) {
+    return map_exception(ix);
+  }
 }
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;

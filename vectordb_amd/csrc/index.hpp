@@ -162,6 +162,9 @@ class Index : public IndexBase {
   int32_t search(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int64_t* ids, float* dist,
                  int32_t* counts, int32_t walk_limit = 0) override;
 
+  // the visible rows in ascending row order, windowed by [skip, skip + limit): SearchByAttribute's full scan (eps_index_select; select.hip)
+  int32_t select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out);
+
   int64_t row_count() const override { return n_rows_; }
   const eps_search_stats& stats() const { return stats_; }
 
@@ -226,6 +229,7 @@ class Index : public IndexBase {
     ~HostBuf();
     bool reserve(size_t bytes);
   } h_out_, h_q_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
+  DevBuf sel_bits_, sel_scan_, sel_out_;   // select(): visibility bitset; block counts | offsets; [count | total | ids] of a call with host result pointers
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   // main-kernel event pairs of the last KRING search calls (read back after a run without a sync inside it);
   // evk0_/evk1_ alias the pair of the call in progress

@@ -95,4 +95,24 @@ void launch_merge_shards(const float* dist, const int64_t* ids, int shards, int6
                          int64_t* out_ids, hipStream_t s, int64_t stride_bytes = 0, int32_t* out_counts = nullptr);
 void launch_fill_u64(u64* p, int64_t n, u64 v, hipStream_t s);
 
+// ---------------------------------------------------------------- ordered select (SearchByAttribute's full scan, :1016-1029; select.hip)
+constexpr int SEL_ROWS = 1024;          // rows per block of the verdict and scatter launches = rows per block count
+constexpr int SEL_THREADS = 256;        // threads of such a block: every wavefront judges SEL_ROWS / SEL_THREADS words of 64 rows
+constexpr int SEL_SCAN_THREADS = 512;   // block counts the scan's one workgroup takes per round of its loop
+inline int64_t select_blocks(int64_t n) { return (n + SEL_ROWS - 1) / SEL_ROWS; }
+struct SelectArgs {
+  FilterSpec f;          // prog_use_dist = 0: @distance reads as 0
+  int64_t n;             // rows [0, n) are judged, 0 < n < 2^31
+  int64_t skip, limit;   // the window over the visible rows' ranks; both <= n
+  int64_t id_base, id_stride;
+  u64* bits;             // [select_blocks(n) * SEL_ROWS / 64] visibility bitset (bit set = visible)
+  u32* counts;           // [select_blocks(n)]
+  int64_t* offsets;      // [select_blocks(n) + 1]
+  int64_t* ids_out;      // [limit]
+  int64_t* count_out;    // [1] clamp(total - skip, 0, limit)
+  int64_t* total_out;    // [1] visible rows of the whole table, or null
+};
+// verdict, scan, scatter (the last only when limit > 0)
+void launch_select(const SelectArgs& a, hipStream_t s);
+
 }  // namespace eps

@@ -372,6 +372,26 @@ class GpuIndex:
         self._check(self.L.eps_index_search(self.h, _ptr(queries), nq, k, C.byref(p), _ptr(ids), _ptr(dist), _ptr(counts)))
         return ids, dist, counts
 
+    def select(self, skip=0, limit=None, out=None):
+        """eps_index_select (SearchByAttribute's full scan, vec_search_executor.cpp:1016-1029): the rows that are not deleted and pass the
+        filter installed last, in ascending row order, ranks [skip, skip + limit) of them (limit=None: all rows).  Returns (ids, total):
+        the window's ids (row * stride + base) and the number of visible rows in the whole table.  out=(ids int64[limit], counts int64[2]):
+        caller-provided buffers, both numpy or both device tensors; counts receives [count, total].  Device buffers are returned as they
+        are - (ids, counts), ids[:counts[0]] valid - and the call is asynchronous on the index's stream."""
+        skip = int(skip)
+        limit = int(self.row_count if limit is None else limit)
+        if out is not None:
+            ids, counts = out
+            _check_select_out(ids, counts, limit)
+        else:
+            ids = np.empty(max(limit, 0), np.int64)
+            counts = np.zeros(2, np.int64)
+        total_ptr = C.c_void_p(_ptr(counts).value + 8)
+        self._check(self.L.eps_index_select(self.h, skip, limit, _ptr(ids), _ptr(counts), total_ptr))
+        if _is_dev(counts):
+            return ids, counts
+        return ids[:int(counts[0])], int(counts[1])
+
     def kernel_times(self, cap=64):
         """main-kernel ms of the most recent search calls (oldest first); synchronises the index's stream"""
         buf = (C.c_double * cap)()
@@ -391,6 +411,19 @@ def _check_out(a, name, shape, dtype):
     if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
         raise ValueError("search: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
                          % (name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+
+
+def _check_select_out(ids, counts, limit):
+    """select's caller-provided buffers: ids int64 [limit] and counts int64 [2], C-contiguous, both NumPy arrays or both device tensors - or a
+    ValueError instead of an out-of-bounds write"""
+    if _is_dev(ids) != _is_dev(counts):
+        raise ValueError("select: out[ids] and out[counts] must both be NumPy arrays or both be device tensors")
+    for a, name, shape in ((ids, "ids", (limit,)), (counts, "counts", (2,))):
+        got_dtype = str(a.dtype).replace("torch.", "")
+        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
+        if got_dtype != "int64" or tuple(a.shape) != shape or not contiguous:
+            raise ValueError("select: out[%s] must be a C-contiguous int64 array of shape %s, got %s %s%s"
+                             % (name, shape, got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
 
 
 def traversal_gather_bytes(stats, dim, avg_degree, seed_evals=0):
@@ -643,4 +676,17 @@ class VecSearchExecutor:
             self.distance_ = np.zeros(n, np.float64)
         self.search_result_[:n] = ids[0, :n]
         self.distance_[:n] = dist[0, :n].astype(np.float64)
+        return 0, n
+
+    def SearchByAttribute(self, total_vector, skip, limit, deleted=None, filter_spec=None):
+        """Status SearchByAttribute(schema, table_segment, skip, limit, primary_keys, filter_nodes, result_size) without a primary-key
+        list (vec_search_executor.cpp:937-1033, full-scan branch :1016-1029): returns (status, result_size); the row ids land in
+        search_result_, in ascending row order."""
+        self._sync(total_vector, deleted, filter_spec)
+        limit = min(int(limit), int(total_vector))   # (:958-961)
+        ids, _ = self._ix.select(skip, limit)
+        n = len(ids)
+        if n > len(self.search_result_):   # (:962-964)
+            self.search_result_ = np.zeros(n, np.int64)
+        self.search_result_[:n] = ids
         return 0, n
