@@ -1,7 +1,7 @@
 """Reference for GpuIndex.select (eps_index_select): which rows are visible, restated in numpy.
 
 The device judges a row with row_visible (csrc/device_common.hpp): deleted bit, then the int-column test, then the compiled program, evaluated on
-a stack of doubles with `@distance` = 0 - ExprEvaluator's rules (query/expr/expr_evaluator.cpp:127-258: every number is a double, booleans are
+a stack of doubles with `@distance` = 0 (a search's judging sites hand it the candidate's fp32 distance: `dist`) - ExprEvaluator's rules (query/expr/expr_evaluator.cpp:127-258: every number is a double, booleans are
 0 / 1, MOD is fmod, a bool attribute is true iff its byte is non-zero).  Here the same program runs over ALL rows at once on a stack of float64
 arrays; comparisons happen in double on both sides, so the two verdicts are equal bit for bit, no tolerance.  Checked on hand-written rows in
 tests/test_select_cpu.py."""
@@ -22,11 +22,28 @@ def as_bytes(rows):
     return rows.view(np.uint8).reshape(rows.shape[0], -1)
 
 
-def eval_program(program, rows):
-    """program: postfix list as GpuIndex.set_filter_program takes it; rows: packed attribute rows.  Returns the final stack value per row
-    (float64 [n]); a row passes iff it is non-zero."""
+# field sizes of the reference's packed attribute rows (FieldTypeSizeMVP; TableSegmentMVP::Init adds them up without padding,
+# table_segment_mvp.cpp:84-86): a schema {BOOL, DOUBLE} puts the double at byte 1
+_FIELDS = {"bool": np.uint8, "i8": np.int8, "i16": np.int16, "i32": np.int32, "i64": np.int64, "f32": np.float32, "f64": np.float64}
+
+
+def row_layout(fields, align=False):
+    """fields: [(name, type)], type a key of _FIELDS -> (structured dtype, {name: byte offset}).  align=False: the reference's packing, one
+    field right after the other; align=True: every field on a multiple of its size (the control layout).  Tests build their rows AND their
+    programs' offsets from this one place."""
+    dt = np.dtype([(name, _FIELDS[t]) for name, t in fields], align=align)
+    return dt, {name: dt.fields[name][1] for name, _ in fields}
+
+
+def eval_program(program, rows, dist=None):
+    """program: postfix list as GpuIndex.set_filter_program takes it; rows: packed attribute rows; dist: what `@distance` reads per row
+    (float64 [n]; the device pushes (double) of its fp32 distance, so callers pass d32.astype(np.float64)), None: 0, as in a select, a mask
+    launch and a pre-filter call.  Returns the final stack value per row (float64 [n]); a row passes iff it is non-zero."""
     raw = as_bytes(rows)
     n = raw.shape[0]
+    if dist is not None:
+        dist = np.asarray(dist, np.float64)
+        assert dist.shape == (n,)
     st = []
     with np.errstate(all="ignore"):
         for ins in program:
@@ -34,7 +51,7 @@ def eval_program(program, rows):
             if op == "const":
                 st.append(np.full(n, float(ins[1]), np.float64))
             elif op == "dist":
-                st.append(np.zeros(n, np.float64))   # LogicalEvaluate(root, id): no distance
+                st.append(np.zeros(n, np.float64) if dist is None else dist.copy())   # (None: LogicalEvaluate(root, id), no distance)
             elif op in _LOADS:
                 dt = np.dtype(_LOADS[op])
                 off = int(ins[1])
@@ -83,7 +100,7 @@ def eval_program(program, rows):
     return st[0]
 
 
-def visible_rows(n, deleted=None, int_filter=None, program=None, rows=None):
+def visible_rows(n, deleted=None, int_filter=None, program=None, rows=None, dist=None):
     """bool [n]: not deleted (bit i & 7 of byte i >> 3), passes `column <op> value` (int_filter = (values, op, value)), passes the program"""
     vis = np.ones(n, bool)
     if deleted is not None:
@@ -92,7 +109,7 @@ def visible_rows(n, deleted=None, int_filter=None, program=None, rows=None):
         col, op, value = int_filter
         vis &= _INT_OPS[op](np.asarray(col)[:n].astype(np.int64), np.int64(value))
     if program:
-        vis &= eval_program(program, rows)[:n] != 0.0
+        vis &= eval_program(program, rows[:n], dist)[:n] != 0.0
     return vis
 
 

@@ -345,6 +345,31 @@ def test_merge_topk(amd):
     for q in range(nq):
         pairs = sorted((float(d[s, q, e]), int(ids[s, q, e])) for s in range(S) for e in range(k) if ids[s, q, e] >= 0)[:k]
         assert [p[1] for p in pairs] == list(oi[q]) and np.allclose([p[0] for p in pairs], od[q])
+    # NaN distances: the merge orders heads as the shards' own keys do (make_key, csrc/device_common.hpp: every NaN ONE ordinal above +inf, then
+    # the id).  Four shards, each list: numbers, +inf, NaN rows, -1 padding; the NaN rows sit in different shards with interleaved ids.
+    # Expected: every number, then +inf, then the NaN rows in id order, then -1 / +inf.  (The mailbox and RCCL exchanges run this kernel.)
+    NAN, INF, S, k = float("nan"), float("inf"), 4, 12
+    lists = [  # (distance, id) per shard, already in the shard's own order
+        [(NAN, 40), (NAN, 44)],                                        # a shard whose FIRST head is a NaN, and it is seen first
+        [(0.5, 1), (2.0, 5), (INF, 9), (NAN, 13), (NAN, 41)],
+        [(-1.0, 2), (0.5, 0), (INF, 6), (-NAN, 10), (NAN, 42)],      # (a NaN with its sign bit set: DOT_PRODUCT's negation)
+        [(1.5, 3), (NAN, 7)],
+    ]
+    pairs = [p for lst in lists for p in lst]
+    want = sorted(p for p in pairs if p[0] == p[0]) + sorted((p for p in pairs if p[0] != p[0]), key=lambda p: p[1])
+    for k in (12, 20):   # 20: longer than everything the shards hold - the padding follows the NaN rows
+        d = np.full((S, 2, k), INF, np.float32)
+        ids = np.full((S, 2, k), -1, np.int64)
+        for s, lst in enumerate(lists):
+            for e, (dd, i) in enumerate(lst):
+                d[s, :, e], ids[s, :, e] = dd, i
+        od, oi = np.empty((2, k), np.float32), np.empty((2, k), np.int64)
+        amd.merge_topk(d, ids, od, oi)
+        wi = ([p[1] for p in want] + [-1] * k)[:k]
+        wd = np.array(([p[0] for p in want] + [INF] * k)[:k], np.float32)
+        for q in range(2):
+            assert list(oi[q]) == wi, (k, list(oi[q]), wi)
+            assert np.array_equal(od[q], wd, equal_nan=True), (k, od[q], wd)
 
 
 # ----------------------------------------------------------------------------------------------- MFMA filter engine

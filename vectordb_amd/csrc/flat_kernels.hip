@@ -627,6 +627,7 @@ __global__ void merge_shards_kernel(const float* dist, const int64_t* ids, int s
   for (int e = 0; e < k; ++e) {
     int best = -1;
     float bd = 0.f;
+    u32 bo = 0;
     int64_t bi = 0;
     for (int s = 0; s < shards; ++s) {
       if (head[s] >= k) continue;
@@ -634,8 +635,11 @@ __global__ void merge_shards_kernel(const float* dist, const int64_t* ids, int s
       const int64_t id = *reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(ids + o) + (stride_bytes ? stride_bytes : nq * k * 8) * s);
       if (id < 0) { head[s] = k; continue; }
       const float d = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(dist + o) + (stride_bytes ? stride_bytes : nq * k * 4) * s);
-      if (best < 0 || d < bd || (d == bd && id < bi)) {
-        best = s; bd = d; bi = id;
+      // heads compare as the shards' own keys do (make_key): the distance's ordinal - every NaN ONE ordinal above +inf - then the id, here the
+      // 64-bit global one.  On raw floats `d < NaN` is false: a NaN head seen first would keep out every number of the shards after it
+      const u32 od = (u32)(make_key(d, 0u) >> 32);
+      if (best < 0 || od < bo || (od == bo && id < bi)) {
+        best = s; bd = d; bo = od; bi = id;
       }
     }
     if (best < 0) {

@@ -477,7 +477,7 @@ int32_t Index::set_filter_program_pitched(const eps_filter_op* ops, int32_t nops
     if (op < EPS_FOP_PUSH_CONST || op > EPS_FOP_NE_BOOL) return fail(EPS_USER_ERROR, "set_filter_program: unknown opcode");
     if (op <= EPS_FOP_PUSH_BOOL) {
       static const int width[] = {0, 0, 0, 1, 2, 4, 8, 4, 8, 1};
-      if (op >= EPS_FOP_PUSH_I8 && (ops[i].arg < 0 || ops[i].arg + width[op] > stride))
+      if (op >= EPS_FOP_PUSH_I8 && (ops[i].arg < 0 || (int64_t)ops[i].arg + width[op] > stride))   // (in 64 bits: arg = INT32_MAX must not wrap)
         return fail(EPS_USER_ERROR, "set_filter_program: attribute offset outside the row");
       uses_dist |= op == EPS_FOP_PUSH_DIST;
       ++sp;
