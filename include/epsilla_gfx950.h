@@ -23,6 +23,8 @@
  *                                   what the caller reads from search_result_ / distance_ (hpp:51-52)
  *   eps_index_select                VecSearchExecutor::SearchByAttribute's full scan (.cpp:1016-1029): the visible rows in row
  *                                   order, windowed by skip / limit
+ *   eps_index_search_range          (new) every row within a distance of the query - what a filter `@distance < r` asks of a Search - with
+ *                                   the count of such rows: the radius query the reference answers by guessing a limit
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -376,6 +378,25 @@ int32_t eps_index_search_walk(eps_index* h, const float* queries, int64_t nq, in
  * search can observe changes (filters, statistics, engine choices).  Three launches (csrc/select.hip): verdict bitset + block counts, scan
  * of the counts, scatter of the window - the reference's loop is serial over all rows (`TODO: leverage multithread to accelerate`, :945). */
 int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out);
+/* Radius search: for every query j the rows that are visible - not deleted, passing the int-column test and the installed program, exactly as for
+ * eps_index_search - and whose exact fp32 distance is <= radius[j].  The exact fp32 distance is the value eps_index_search in EPS_MODE_FLAT returns
+ * for that (row, query), bit for bit; a program's `@distance` reads the same value, on every engine.  queries: host or device float[nq][dim]
+ * (COSINE: already normalised); radius: HOST float[nq], NaN is EPS_USER_ERROR, +inf is allowed.  totals_out[j] (may be NULL) = the number of such
+ * rows, whatever cap is; counts_out[j] = min(total, cap); ids_out[j][0 .. count) / dist_out[j][0 .. count) = the count smallest in ascending
+ * (distance, id) order - the library's one key order, ids through eps_index_set_id_map - the unused slots -1 / +inf.  So total <= cap: the answer
+ * is complete; total > cap: the cap closest, and the caller knows how many are missing.  ids_out [nq][cap], dist_out [nq][cap], counts_out [nq]
+ * (may be NULL), totals_out [nq]: host or device, all the same kind - device: on the index's stream, the caller synchronises; host: the call
+ * synchronises.  1 <= cap <= 8192 (one workgroup orders a query's keys in LDS); nq = 0: EPS_OK; an empty table: counts and totals 0.  p: only
+ * flat_engine is read (NULL: defaults) - EPS_FLAT_STREAM scans the fp32 rows; EPS_FLAT_MFMA / EPS_FLAT_MFMA_I8 run ONE launch of the lower-bound
+ * filter over the fp16 / 8-bit mirror with thresholds from the radii, then give the rows that passed their exact distance (csrc/range.hip); a
+ * table the mirror cannot serve falls to the next form, as in a search; EPS_FLAT_AUTO chooses as a search does.  All forms return the same bits.
+ * A query whose candidate list overflowed runs again on the stream form, one whose total exceeds cap takes its cap closest from the flat scan:
+ * both are counted in eps_search_stats::overflow_queries; no list ever silently loses a row.  eps_index_last_stats reports the call like a search
+ * (main_kernel_*, main_kernel_bits 8 / 16 / 32, rerank_rows = candidates given an exact distance; main_kernel_ms times the pass - the filter launch
+ * of the last slice of 2048 queries, or the stream scan - never a fall-back's scan).  A sharded handle: EPS_DB_UNSUPPORTED_ERROR;
+ * after an append, a stale bitset / column / attribute rows: EPS_USER_ERROR.  Nothing a later search can observe changes. */
+int32_t eps_index_search_range(eps_index* h, const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p,
+                               int64_t* ids_out, float* dist_out, int32_t* counts_out, int64_t* totals_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

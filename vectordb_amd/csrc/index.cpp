@@ -945,6 +945,209 @@ int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* co
   return EPS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ search_range
+// Every visible row with exact fp32 distance <= radius[j]: the total, and the cap closest by (distance, id).  One pass finds the survivors - the
+// matrix form (one launch of the lower-bound filter + the exact tail, flat_range_lists) or the stream form (range_scan_kernel) - one launch orders
+// them (range.hip), one host sync reads every query's status and total (host outputs: a second one brings the results, once).  What is left to the host after it, both counted in overflow_queries:
+//   RANGE_RESCAN  the filter's candidate list was too short: the query runs again on the stream form;
+//   RANGE_TOPK    more survivors than cap: the cap closest come from flat_stream (k = cap), the total is already counted.
+// Reports like a search (statistics, kernel ring); changes nothing a later search can observe.
+int32_t Index::search_range(const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* pp, int64_t* ids, float* dist,
+                            int32_t* counts, int64_t* totals) {
+  eps_search_params p;
+  if (pp) p = *pp; else eps_default_search_params(&p);
+  if (nq < 0) return fail(EPS_USER_ERROR, "search_range: nq must be >= 0");
+  if (cap < 1 || cap > RANGE_MAX_CAP) return fail(EPS_USER_ERROR, "search_range: cap must be in [1, 8192]");
+  if (nq == 0) return EPS_OK;
+  if (!queries || !radius || !ids || !dist) return fail(EPS_USER_ERROR, "search_range: null buffer");
+  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_range: unknown flat engine");
+  HIP_TRY(hipSetDevice(device_));
+  if (is_device_ptr(radius)) return fail(EPS_USER_ERROR, "search_range: radius must be a host array");
+  for (int64_t j = 0; j < nq; ++j)
+    if (radius[j] != radius[j]) return fail(EPS_USER_ERROR, "search_range: a radius is NaN");
+  if (d_deleted_ && deleted_bytes_ < (n_rows_ + 7) / 8)
+    return fail(EPS_USER_ERROR, "search_range: the deleted bitset is shorter than the table (rows were appended): call set_deleted again");
+  if (f_op_ && d_fcol_ && fcol_rows_ < n_rows_)
+    return fail(EPS_USER_ERROR, "search_range: the filter column is shorter than the table (rows were appended): call set_int_filter again");
+  if (prog_len_ > 0 && prog_rows_n_ < n_rows_)
+    return fail(EPS_USER_ERROR, "search_range: the filter program's attribute rows are shorter than the table (rows were appended): call set_filter_program again");
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)) || (totals && out_dev != is_device_ptr(totals)))
+    return fail(EPS_USER_ERROR, "search_range: ids_out, dist_out, counts_out and totals_out must all be host or all be device pointers");
+  std::memset(&stats_, 0, sizeof(stats_));
+  stage_n_ = 0;
+  walk_limit_ = 0;
+  prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
+  kring_seq_ += 1;
+  {
+    const int slot = (int)(kring_seq_ % KRING);
+    evk0_ = kring_[slot][0];
+    evk1_ = kring_[slot][1];
+    kring_valid_[slot] = false;
+  }
+  const int64_t n = n_rows_;
+
+  // ---- scratch.  Device: [counts | status | candidates re-ranked], [radii | fall-back query numbers]; page-locked: [radii | read-back | query numbers]
+  const size_t rb_bytes = (((size_t)nq * 8 + 7) & ~(size_t)7) + 8, rad_bytes = ((size_t)nq * 4 + 7) & ~(size_t)7;
+  const size_t ids_bytes = (size_t)nq * cap * sizeof(int64_t), tot_bytes = (size_t)nq * sizeof(int64_t), dist_bytes = (size_t)nq * cap * sizeof(float);
+  const size_t out_bytes = ids_bytes + tot_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
+  if (!rng_keys_.reserve((size_t)nq * cap * sizeof(u64)) || !rng_cnt_.reserve(rb_bytes) || !rng_in_.reserve(2 * rad_bytes) ||
+      (!out_dev && !rng_out_.reserve(out_bytes)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (scratch)");
+  if (!h_rng_.reserve(2 * rad_bytes + rb_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of page-locked host memory");
+  float* h_rad = static_cast<float*>(h_rng_.p);
+  u32* h_rb = reinterpret_cast<u32*>(static_cast<char*>(h_rng_.p) + rad_bytes);
+  int32_t* h_sel = reinterpret_cast<int32_t*>(static_cast<char*>(h_rng_.p) + rad_bytes + rb_bytes);
+  u32* d_cnt = rng_cnt_.as<u32>();
+  u32* d_status = d_cnt + nq;
+  unsigned long long* d_cand_total = reinterpret_cast<unsigned long long*>(rng_cnt_.as<char>() + rb_bytes - 8);
+  int32_t* d_sel = reinterpret_cast<int32_t*>(rng_in_.as<char>() + rad_bytes);
+
+  const float* dq = queries;
+  if (!is_device_ptr(queries)) {   // (as search() uploads them)
+    const size_t qb = (size_t)nq * dim_ * sizeof(float);
+    if (!q_buf_.reserve(qb)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (queries)");
+    if (!(tune_int("EPS_HOST_STAGING", 1) == 0) && qb <= ((size_t)256 << 10) && h_q_.reserve(qb)) {
+      HIP_TRY(hipStreamSynchronize(stream_));
+      memcpy(h_q_.p, queries, qb);
+      HIP_TRY(hipMemcpyAsync(q_buf_.p, h_q_.p, qb, hipMemcpyHostToDevice, stream_));
+    } else {
+      HIP_TRY(hipMemcpyAsync(q_buf_.p, queries, qb, hipMemcpyHostToDevice, stream_));
+    }
+    dq = q_buf_.as<float>();
+  }
+  HIP_TRY(hipStreamSynchronize(stream_));   // (the previous call's copies out of / into h_rng_ have completed)
+  memcpy(h_rad, radius, (size_t)nq * 4);
+  HIP_TRY(hipMemcpyAsync(rng_in_.p, h_rad, (size_t)nq * 4, hipMemcpyHostToDevice, stream_));
+  HIP_TRY(hipMemsetAsync(rng_cnt_.p, 0, rb_bytes, stream_));
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  const RangeLists L{rng_keys_.as<u64>(), d_cnt, rng_in_.as<float>(), cap};
+  const FilterSpec fs = filter_spec();
+  int64_t* d_ids = ids;
+  float* d_dist = dist;
+  int32_t* d_counts = counts;
+  int64_t* d_totals = totals;
+  if (!out_dev) {
+    d_ids = rng_out_.as<int64_t>();
+    d_totals = reinterpret_cast<int64_t*>(rng_out_.as<char>() + ids_bytes);
+    d_dist = reinterpret_cast<float*>(rng_out_.as<char>() + ids_bytes + tot_bytes);
+    d_counts = reinterpret_cast<int32_t*>(rng_out_.as<char>() + ids_bytes + tot_bytes + dist_bytes);
+  }
+  // the stream form over the `m` queries named by sel (null: all of them), in launches of at most 32768 queries (the grid's y extent)
+  auto scan = [&](const int32_t* sel, int64_t m) {
+    for (int64_t q0 = 0; q0 < m; q0 += 32768) {
+      RangeScanArgs a{d_rows_, n, (int)dim_, metric_, dq, std::min<int64_t>(32768, m - q0), sel ? sel + q0 : nullptr, fs, L};
+      if (!sel) {   // (query numbers count from the launch's first query)
+        a.queries = dq + q0 * dim_;
+        a.L = RangeLists{L.keys + q0 * cap, L.cnt + q0, L.radius + q0, cap};
+      }
+      launch_range_scan(a, stream_);
+    }
+    stats_.dist_evals += m * n;
+  };
+  auto order = [&](const int32_t* sel, int64_t m, const u64* topk) {
+    launch_range_order(RangeOrderArgs{m, sel, L, topk, d_status, id_base_, id_stride_, d_ids, d_dist, d_counts, d_totals}, stream_);
+  };
+  auto read_back = [&]() -> hipError_t {
+    const hipError_t er = hipMemcpyAsync(h_rb, rng_cnt_.p, rb_bytes, hipMemcpyDeviceToHost, stream_);   // (status and totals only: the results cross PCIe once, at the end)
+    return er == hipSuccess ? hipStreamSynchronize(stream_) : er;
+  };
+  auto pick = [&](u32 status, std::vector<int32_t>* sel) -> hipError_t {   // the queries left in `status`, their numbers on the device
+    sel->clear();
+    for (int64_t j = 0; j < nq; ++j)
+      if (h_rb[nq + j] == status) sel->push_back((int32_t)j);
+    if (sel->empty()) return hipSuccess;
+    memcpy(h_sel, sel->data(), sel->size() * 4);
+    return hipMemcpyAsync(d_sel, h_sel, sel->size() * 4, hipMemcpyHostToDevice, stream_);
+  };
+
+  // ---- the pass
+  int engine = p.flat_engine;
+  bool matrix = engine == EPS_FLAT_MFMA || engine == EPS_FLAT_MFMA_I8;
+  if (engine == EPS_FLAT_AUTO) {   // (the rule counts single-query calls towards building a mirror: that is a search's business)
+    const int64_t keep_version = small_calls_version_;
+    const int keep_calls = small_calls_;
+    matrix = flat_mfma_profitable(*this, nq, 1);
+    small_calls_version_ = keep_version;
+    small_calls_ = keep_calls;
+  }
+  bool served = false;
+  if (matrix) {
+    const int32_t rc = flat_range_lists(*this, dq, nq, engine == EPS_FLAT_MFMA ? 16 : (engine == EPS_FLAT_MFMA_I8 ? 8 : 0), L, d_cand_total, &served);
+    if (rc != EPS_OK) return rc;
+  }
+  if (!served && n > 0) {
+    HIP_TRY(hipEventRecord(evk0_, stream_));
+    scan(nullptr, nq);
+    HIP_TRY(hipEventRecord(evk1_, stream_));
+    stats_.main_kernel_launches = 1;
+    stats_.main_kernel_rows = n;
+    stats_.main_kernel_queries = nq;
+    stats_.main_kernel_bits = 32;
+  }
+  order(nullptr, nq, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(read_back());
+  stats_.rerank_rows = (int64_t)*reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(h_rb) + rb_bytes - 8);
+
+  // ---- what the lists could not answer
+  const eps_search_stats pass_stats = stats_;
+  std::vector<int32_t> sel;
+  int64_t fell_back = 0;
+  HIP_TRY(pick(RANGE_RESCAN, &sel));
+  if (!sel.empty()) {
+    fell_back += (int64_t)sel.size();
+    launch_range_gather(dq, (int)dim_, d_sel, (int64_t)sel.size(), nullptr, d_cnt, true, stream_);
+    scan(d_sel, (int64_t)sel.size());
+    order(d_sel, (int64_t)sel.size(), nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(read_back());
+  }
+  std::vector<int32_t> rescanned;
+  rescanned.swap(sel);
+  HIP_TRY(pick(RANGE_TOPK, &sel));
+  if (!sel.empty()) {
+    const int64_t m = (int64_t)sel.size();
+    fell_back += m;
+    for (int32_t j : sel) fell_back -= std::binary_search(rescanned.begin(), rescanned.end(), j) ? 1 : 0;   // (a query counts once)
+    if (!tmp_buf_.reserve((size_t)m * dim_ * sizeof(float)) || !run_buf_.reserve((size_t)m * cap * sizeof(u64)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (fall-back)");
+    launch_range_gather(dq, (int)dim_, d_sel, m, tmp_buf_.as<float>(), d_cnt, false, stream_);
+    // (flat_stream times its scan with the call's main-kernel events: it gets a spare pair - no filter stage of this call uses one - so that
+    // main_kernel_ms stays the time of the pass, as the other main_kernel_* fields do)
+    hipEvent_t const k0 = evk0_, k1 = evk1_;
+    evk0_ = stage_ev_[STAGE_EV - 1][0];
+    evk1_ = stage_ev_[STAGE_EV - 1][1];
+    const int32_t rc = flat_stream(tmp_buf_.as<float>(), m, cap, 0, n, run_buf_.as<u64>(), false);
+    evk0_ = k0;
+    evk1_ = k1;
+    if (rc != EPS_OK) return rc;
+    order(d_sel, m, run_buf_.as<u64>());
+    HIP_TRY(hipGetLastError());
+  }
+  if (fell_back > 0) {   // the call's main kernel stays the pass
+    stats_.main_kernel_launches = pass_stats.main_kernel_launches;
+    stats_.main_kernel_rows = pass_stats.main_kernel_rows;
+    stats_.main_kernel_queries = pass_stats.main_kernel_queries;
+    stats_.main_kernel_bits = pass_stats.main_kernel_bits;
+  }
+  stats_.overflow_queries = fell_back;
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    if (!h_out_.reserve(out_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of page-locked host memory (results)");
+    HIP_TRY(hipMemcpyAsync(h_out_.p, rng_out_.p, out_bytes, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    const char* h = static_cast<const char*>(h_out_.p);
+    memcpy(ids, h, ids_bytes);
+    if (totals) memcpy(totals, h + ids_bytes, tot_bytes);
+    memcpy(dist, h + ids_bytes + tot_bytes, dist_bytes);
+    if (counts) memcpy(counts, h + ids_bytes + tot_bytes + dist_bytes, (size_t)nq * sizeof(int32_t));
+  }
+  kring_valid_[kring_seq_ % KRING] = stats_.main_kernel_launches > 0;
+  return EPS_OK;
+}
+
 int32_t Index::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   // event timings are read lazily: the caller may have left the work in flight
@@ -1224,6 +1427,17 @@ int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids
   if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, "select: single-device indices only (a sharded table is not served)");
   try {
     return ix->select(skip, limit, ids_out, count_out, total_out);
+  } catch (...) {
+    return map_exception(ix);
+  }
+}
+int32_t eps_index_search_range(eps_index* h, const float* q, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p, int64_t* ids,
+                               float* dist, int32_t* counts, int64_t* totals) {
+  if (!h) return EPS_USER_ERROR;
+  Index* ix = dynamic_cast<Index*>(IX(h));
+  if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, "search_range: single-device indices only (a sharded table is not served)");
+  try {
+    return ix->search_range(q, nq, radius, cap, p, ids, dist, counts, totals);
   } catch (...) {
     return map_exception(ix);
   }

@@ -164,6 +164,9 @@ class Index : public IndexBase {
 
   // the visible rows in ascending row order, windowed by [skip, skip + limit): SearchByAttribute's full scan (eps_index_select; select.hip)
   int32_t select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out);
+  // every visible row within radius[j] of query j: the total, and the cap closest in (distance, id) order (eps_index_search_range; range.hip)
+  int32_t search_range(const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p, int64_t* ids_out, float* dist_out,
+                       int32_t* counts_out, int64_t* totals_out);
 
   int64_t row_count() const override { return n_rows_; }
   const eps_search_stats& stats() const { return stats_; }
@@ -228,8 +231,11 @@ class Index : public IndexBase {
     size_t cap = 0;
     ~HostBuf();
     bool reserve(size_t bytes);
-  } h_out_, h_q_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
+  } h_out_, h_q_, h_rng_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
   DevBuf sel_bits_, sel_scan_, sel_out_;   // select(): visibility bitset; block counts | offsets; [count | total | ids] of a call with host result pointers
+  // search_range(): survivor keys [nq][cap]; survivor counts | status | candidates re-ranked (what the host reads back); radii | fall-back query
+  // numbers; [ids | distances | counts | totals] of a call with host result pointers.  h_rng_: the page-locked side of the middle two
+  DevBuf rng_keys_, rng_cnt_, rng_in_, rng_out_;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   // main-kernel event pairs of the last KRING search calls (read back after a run without a sync inside it);
   // evk0_/evk1_ alias the pair of the call in progress
@@ -286,6 +292,9 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k);  // AUTO heuristi
 int32_t flat_mirror_view(Index& ix, int bits, const float* queries, int64_t nq, eps_mirror_view* v);
 int32_t flat_filter_pass(Index& ix, const float* queries, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
                          void* T_out, u32* cnt_out, void* cand_out);
+// the matrix form of a radius search (Index::search_range): one filter launch per slice of queries with thresholds from L.radius, then the exact
+// tail into the survivor lists L; *cand_total += rows given an exact distance.  *served = false: no usable mirror - nothing was launched
+int32_t flat_range_lists(Index& ix, const float* dq, int64_t nq, int bits, const RangeLists& L, unsigned long long* cand_total, bool* served);
 int32_t quant8_view(Index& ix, Quant8View* v);
 void quant8_queries(Index& ix, const Quant8View& v, const float* dq, int64_t nq, signed char* q8, float* qstat);
 void half_mirror_free(HalfMirror* m);

@@ -115,4 +115,56 @@ struct SelectArgs {
 // verdict, scan, scatter (the last only when limit > 0)
 void launch_select(const SelectArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- radius search (eps_index_search_range; range.hip)
+constexpr int RANGE_MAX_CAP = 8192;          // results per query: one workgroup orders a query's keys in LDS, 64 KB of them
+constexpr u32 RANGE_CNT_RESCAN = ~0u;        // a query's survivor count while its candidate list was too short to be trusted
+enum : u32 { RANGE_DONE = 0, RANGE_RESCAN = 1, RANGE_TOPK = 2 };   // per-query status the order launch leaves for the host
+// the survivors of every query: rows with dist <= radius that are visible.  cnt[j] counts ALL of them (the query's total), the first `cap` to
+// arrive have their (distance, row) key in keys[j][..], in no order.
+struct RangeLists {
+  u64* keys;             // [nq][cap]
+  u32* cnt;              // [nq]
+  const float* radius;   // [nq]
+  int cap;
+};
+struct RangeRerankArgs {   // the tail of the matrix form: exact distances of the filter pass's candidates
+  const float* rows;
+  int dim, metric;
+  const float* queries;    // [nq][dim]
+  int64_t nq;
+  FilterSpec f;
+  const u32* cand;         // [nq][cand_cap] row ids, unordered
+  const u32* cand_count;   // [nq] rows that passed the filter (may exceed cand_cap)
+  int cand_cap;
+  RangeLists L;
+  unsigned long long* cand_total;   // [1] += candidates given an exact distance
+};
+void launch_range_rerank(const RangeRerankArgs& a, hipStream_t s);
+struct RangeScanArgs {     // the stream form: every row against blocks of queries
+  const float* rows;
+  int64_t n;
+  int dim, metric;
+  const float* queries;    // [..][dim], indexed by query number
+  int64_t nq;              // queries of this launch
+  const int32_t* qsel;     // [nq] their query numbers, or null: 0 .. nq - 1
+  FilterSpec f;
+  RangeLists L;            // indexed by query number
+};
+void launch_range_scan(const RangeScanArgs& a, hipStream_t s);
+struct RangeOrderArgs {
+  int64_t nq;              // queries of this launch
+  const int32_t* qsel;     // [nq] their query numbers, or null
+  RangeLists L;
+  const u64* topk;         // null: order the query's list (where it holds every survivor); else [nq][cap] sorted keys of launch-local query i: cut at the radius
+  u32* status;             // [..] RANGE_*, by query number
+  int64_t id_base, id_stride;
+  int64_t* ids_out;        // [..][cap]
+  float* dist_out;         // [..][cap]
+  int32_t* counts_out;     // [..] or null
+  int64_t* totals_out;     // [..] or null
+};
+void launch_range_order(const RangeOrderArgs& a, hipStream_t s);
+// the queries named by qsel, copied next to each other (out, may be null); zero_cnt: their survivor counts start again at 0
+void launch_range_gather(const float* queries, int dim, const int32_t* qsel, int64_t m, float* out, u32* cnt, bool zero_cnt, hipStream_t s);
+
 }  // namespace eps

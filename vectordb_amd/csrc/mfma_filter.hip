@@ -785,6 +785,33 @@ int32_t flat_mirror_view(Index& ix, int bits, const float* hq, int64_t nq, eps_m
   return er == hipSuccess ? EPS_OK : ix.hip_fail(er, "mirror_view");
 }
 
+// ---- what a single pass with IMPOSED thresholds is made of (flat_filter_pass below, the radius search behind it)
+// every query's threshold from a distance - keys[j] = make_key(distance, 0), k = 1 - by the chain's own kernels (which also zero the candidate
+// counts and the group counters), or (pad_only) the padding entries alone
+static void launch_pass_thresholds(const Index& ix, const HalfMirror& m, const Chain& c, const u64* keys, int pad_only) {
+  hipStream_t s = ix.stream_;
+  const dim3 tgrid((unsigned)((c.b_pad + 255) / 256));
+  if (c.i8)
+    hipLaunchKernelGGL(threshold8_kernel, tgrid, dim3(256), 0, s, keys, 1, c.nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, c.u8, m.T.as<int>(), c.c.cnt,
+                       m.gsync.as<u32>(), c.slack, c.approx ? 1 : 0, pad_only);
+  else
+    hipLaunchKernelGGL(threshold_kernel, tgrid, dim3(256), 0, s, keys, 1, c.nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, m.T.as<float>(), c.c.cnt,
+                       m.gsync.as<u32>(), c.slack, c.approx ? 1 : 0, pad_only);
+}
+// the group counters' start state and ONE filter launch over the row tiles of [lo, hi) against the thresholds in m.T
+static hipError_t launch_pass(const Index& ix, const HalfMirror& m, const Chain& c, int64_t lo, int64_t hi, bool dense) {
+  hipStream_t s = ix.stream_;
+  const hipError_t er = hipMemsetAsync(m.gsync.p, 0, 1024, s);
+  if (er != hipSuccess) return er;
+  FilterArgs fa = filter_args(ix, m, c);
+  fa.tile0 = lo / BM3;
+  fa.ntiles = (hi + BM3 - 1) / BM3 - fa.tile0;
+  fa.row_hi = hi;
+  fa.dense = dense ? 1 : 0;
+  launch_filter(m, c, fa, s);
+  return hipSuccess;
+}
+
 int32_t flat_filter_pass(Index& ix, const float* hq, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
                          void* T_out, u32* cnt_out, void* cand_out) {
   if (bits != 8 && bits != 16) return ix.fail(EPS_USER_ERROR, "filter_pass: bits must be 8 or 16");
@@ -824,26 +851,14 @@ int32_t flat_filter_pass(Index& ix, const float* hq, int64_t nq, int bits, int64
     if (er == hipSuccess) er = hipStreamSynchronize(s);
     if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: thresholds");
   }
-  const dim3 tgrid((unsigned)((c.b_pad + 255) / 256));
-  if (i8)
-    hipLaunchKernelGGL(threshold8_kernel, tgrid, dim3(256), 0, s, keys.as<u64>(), 1, nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, c.u8, m.T.as<int>(), c.c.cnt,
-                       m.gsync.as<u32>(), c.slack, approx ? 1 : 0, pad_only);
-  else
-    hipLaunchKernelGGL(threshold_kernel, tgrid, dim3(256), 0, s, keys.as<u64>(), 1, nq, c.b_pad, m.qstat.as<float>(), c.maxima(m), ix.metric_, m.T.as<float>(), c.c.cnt,
-                       m.gsync.as<u32>(), c.slack, approx ? 1 : 0, pad_only);
+  launch_pass_thresholds(ix, m, c, keys.as<u64>(), pad_only);
   if (pad_only) {
     if (mode != EPS_PASS_DENSE) er = hipMemcpyAsync(m.T.p, thr, (size_t)nq * 4, hipMemcpyHostToDevice, s);
     else er = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.T.p), 0x7F800000, (size_t)nq, s);   // (the seed pass's start state; the dense form reads no threshold)
     if (er == hipSuccess) er = hipMemsetAsync(c.c.cnt, 0, (size_t)nq * 4, s);
   }
-  if (er == hipSuccess) er = hipMemsetAsync(m.gsync.p, 0, 1024, s);
+  if (er == hipSuccess) er = launch_pass(ix, m, c, lo, hi, mode == EPS_PASS_DENSE);
   if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: start state");
-  FilterArgs fa = filter_args(ix, m, c);
-  fa.tile0 = lo / BM3;
-  fa.ntiles = (hi + BM3 - 1) / BM3 - fa.tile0;
-  fa.row_hi = hi;
-  fa.dense = mode == EPS_PASS_DENSE ? 1 : 0;
-  launch_filter(m, c, fa, s);
   er = hipGetLastError();
   if (er != hipSuccess) return ix.hip_fail(er, "filter_pass: launch");
   if (T_out) er = hipMemcpyAsync(T_out, m.T.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
@@ -853,6 +868,78 @@ int32_t flat_filter_pass(Index& ix, const float* hq, int64_t nq, int bits, int64
   if (er != hipSuccess) return ix.hip_fail(er, "filter_pass");
   if (mode == EPS_PASS_DENSE)
     for (int64_t j = 0; j < nq; ++j) cnt_out[j] = (u32)(hi - lo);
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ radius search, matrix form
+// eps_index_search_range (Index::search_range): a radius query knows its threshold before the first row is read, so the chain's seed pass and
+// stages collapse into ONE filter launch over all rows - thresholds from the radii in the exact-mode, distance form (as flat_filter_pass builds
+// them: every row whose exact distance is <= r passes) - and the exact tail (range.hip) into the survivor lists L.  Slices as flat_mfma_search.
+__global__ void range_keys_kernel(const float* radius, int64_t nq, u64* keys) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < nq) keys[j] = make_key(radius[j], 0u);
+}
+
+// candidate slots per query of the filter launch: 4 x cap, and never fewer than fit the scratch the chain reserves anyway (plan_chain: 4096 slots
+// of 8 bytes = 8192 row ids).  A performance knob: a query whose list overflows is answered by the stream form
+static int range_cand_cap(int cap) { return std::max(8192, 4 * cap); }
+
+static int32_t range_slice(Index& ix, HalfMirror& m, bool i8, const float* dq, int64_t nq, const RangeLists& L, unsigned long long* cand_total) {
+  hipStream_t s = ix.stream_;
+  const int64_t n = ix.n_rows_;
+  Chain c;
+  int32_t rc = plan_chain(ix, m, dq, nq, 1, nullptr, false, 1, i8, n, &c);
+  if (rc != EPS_OK) return rc;
+  c.cap = range_cand_cap(L.cap);
+  if (!m.cand.reserve((size_t)nq * (size_t)c.cap * 4) || !m.seedc.reserve((size_t)nq * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (candidates)");
+  rc = prepare_queries(ix, m, c);
+  if (rc != EPS_OK) return rc;
+  ensure_filter_kernels(ix, m);
+  m.s8_clean_cnt = nullptr;   // (the pass's counters live where the one-pass form keeps its own)
+  u64* keys = m.seedc.as<u64>();   // (the seed stage's lists: no seeds here)
+  hipLaunchKernelGGL(range_keys_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, L.radius, nq, keys);
+  launch_pass_thresholds(ix, m, c, keys, 0);
+  (void)hipEventRecord(ix.evk0_, s);
+  const hipError_t er = launch_pass(ix, m, c, 0, n, false);
+  if (er != hipSuccess) return ix.hip_fail(er, "search_range: start state");
+  (void)hipEventRecord(ix.evk1_, s);
+  ix.stats_.main_kernel_launches += 1;
+  ix.stats_.main_kernel_rows = n;
+  ix.stats_.main_kernel_queries = nq;
+  ix.stats_.main_kernel_bits = i8 ? 8 : 16;
+  ix.stats_.dist_evals += nq * n;
+  RangeRerankArgs ra{ix.d_rows_, (int)ix.dim_, ix.metric_, dq, nq, c.fs, m.cand.as<u32>(), c.c.cnt, c.cap, L, cand_total};
+  launch_range_rerank(ra, s);
+  return EPS_OK;
+}
+
+int32_t flat_range_lists(Index& ix, const float* dq, int64_t nq, int bits, const RangeLists& L, unsigned long long* cand_total, bool* served) {
+  *served = false;
+  if (ix.n_rows_ <= 0) return EPS_OK;
+  const bool auto_bits = bits != 8 && bits != 16;
+  // the chain's own decisions: an 8-bit table that declines falls to fp16, fp16 out of range to the stream form
+  bool i8 = bits != 16;
+  int32_t rc = EPS_OK;
+  if (i8) {
+    rc = ensure_mirror8(ix);
+    if (rc != EPS_OK) return rc;
+    if (!ix.mirror_->i8_ok || (auto_bits && ix.mirror_->i8_overflows >= 3)) i8 = false;
+  }
+  if (!i8) {
+    rc = ensure_mirror(ix);
+    if (rc != EPS_OK) return rc;
+    if (!ix.mirror_->fp16_range_ok) return EPS_OK;
+  }
+  HalfMirror& m = *ix.mirror_;
+  const int64_t slice = std::max(256, tune_int("EPS_MFMA_MAX_BATCH", 2048));
+  for (int64_t q0 = 0; q0 < nq; q0 += slice) {
+    const RangeLists Ls{L.keys + q0 * L.cap, L.cnt + q0, L.radius + q0, L.cap};
+    rc = range_slice(ix, m, i8, dq + q0 * ix.dim_, std::min(slice, nq - q0), Ls, cand_total);
+    if (rc != EPS_OK) return rc;
+  }
+  const hipError_t er = hipGetLastError();
+  if (er != hipSuccess) return ix.hip_fail(er, "search_range: matrix form");
+  *served = true;
   return EPS_OK;
 }
 

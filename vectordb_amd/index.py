@@ -392,6 +392,41 @@ class GpuIndex:
             return ids, counts
         return ids[:int(counts[0])], int(counts[1])
 
+    def search_range(self, queries, radius, cap, flat_engine="auto", out=None):
+        """eps_index_search_range: per query the visible rows whose exact fp32 distance is <= its radius (a scalar, or one per query).  Returns
+        (ids int64[nq, cap], dist float32[nq, cap], counts int32[nq], totals int64[nq]): totals = how many such rows there are, counts =
+        min(totals, cap), and the counts closest in ascending (distance, id) order, the rest -1 / +inf.  flat_engine: "auto" | "stream" | "mfma" |
+        "mfma_i8" (or a FLAT_* value): the same bits from all of them.  NumPy queries give NumPy results; device queries give device tensors and
+        the call is asynchronous on the index's stream.  out=(ids, dist, counts, totals): caller-provided buffers, all NumPy or all device."""
+        engine = RANGE_ENGINES[flat_engine]
+        cap = int(cap)
+        dev = _is_dev(queries)
+        if not dev:
+            queries = np.ascontiguousarray(queries, np.float32)
+            if queries.ndim == 1:
+                queries = queries[None, :]
+        nq = queries.shape[0]
+        assert queries.shape[1] == self.dim
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)))
+        if out is not None:
+            ids, dist, counts, totals = out
+            _check_range_out(ids, dist, counts, totals, nq, cap)
+        elif dev:
+            import torch
+            ids = torch.empty((nq, cap), dtype=torch.int64, device=queries.device)
+            dist = torch.empty((nq, cap), dtype=torch.float32, device=queries.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+            totals = torch.empty((nq,), dtype=torch.int64, device=queries.device)
+        else:
+            ids = np.empty((nq, max(cap, 0)), np.int64)
+            dist = np.empty((nq, max(cap, 0)), np.float32)
+            counts = np.empty(nq, np.int32)
+            totals = np.empty(nq, np.int64)
+        p = self.params(flat_engine=engine)
+        self._check(self.L.eps_index_search_range(self.h, _ptr(queries), nq, _ptr(radius), cap, C.byref(p), _ptr(ids), _ptr(dist), _ptr(counts),
+                                                  _ptr(totals)))
+        return ids, dist, counts, totals
+
     def kernel_times(self, cap=64):
         """main-kernel ms of the most recent search calls (oldest first); synchronises the index's stream"""
         buf = (C.c_double * cap)()
@@ -411,6 +446,24 @@ def _check_out(a, name, shape, dtype):
     if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
         raise ValueError("search: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
                          % (name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+
+
+RANGE_ENGINES = {"auto": FLAT_AUTO, "stream": FLAT_STREAM, "mfma": FLAT_MFMA, "mfma_i8": FLAT_MFMA_I8,
+                 FLAT_AUTO: FLAT_AUTO, FLAT_STREAM: FLAT_STREAM, FLAT_MFMA: FLAT_MFMA, FLAT_MFMA_I8: FLAT_MFMA_I8}
+
+
+def _check_range_out(ids, dist, counts, totals, nq, cap):
+    """search_range's caller-provided buffers: ids int64 [nq, cap], dist float32 [nq, cap], counts int32 [nq], totals int64 [nq], C-contiguous, all
+    NumPy arrays or all device tensors - or a ValueError instead of an out-of-bounds write"""
+    bufs = ((ids, "ids", (nq, cap), "int64"), (dist, "dist", (nq, cap), "float32"), (counts, "counts", (nq,), "int32"), (totals, "totals", (nq,), "int64"))
+    if len({_is_dev(a) for a, _, _, _ in bufs}) != 1:
+        raise ValueError("search_range: out[ids], out[dist], out[counts] and out[totals] must all be NumPy arrays or all be device tensors")
+    for a, name, shape, dtype in bufs:
+        got_dtype = str(a.dtype).replace("torch.", "")
+        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
+        if got_dtype != dtype or tuple(a.shape) != shape or not contiguous:
+            raise ValueError("search_range: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
+                             % (name, dtype, shape, got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
 
 
 def _check_select_out(ids, counts, limit):
