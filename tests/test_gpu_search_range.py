@@ -86,6 +86,28 @@ def test_integer_tables_equal_numpy_on_every_engine(metric, n, appended, d, nq):
     ix.close()
 
 
+# ---- 1b. host results come back as one block [ids | totals | distances | counts]: in one page-locked copy split on the host, or - EPS_HOST_STAGING=0,
+# and where page-locked memory cannot be had - in one pageable copy per array.  Both split the block the same way.
+@pytest.mark.parametrize("staging", [None, "0"])
+def test_host_results_with_and_without_page_locked_staging(monkeypatch, staging):
+    if staging is None:
+        monkeypatch.delenv("EPS_HOST_STAGING", raising=False)
+    else:
+        monkeypatch.setenv("EPS_HOST_STAGING", staging)
+    n, d, nq, cap = 1000, 19, 3, 64
+    X, Q = er.make("integers -8..8", n, d, nq, seed=0)
+    d32 = rr.dist32(X, Q, 0)
+    radius, got = mixed_radii(d32, ("one", "few", "all"))
+    want = rr.numpy_range(d32, radius, cap)
+    over = int((want[3] > cap).sum())
+    assert over > 0 and (want[2] < cap).any()   # (full and partly filled lists: a part read at the wrong offset shows)
+    ix = index(X, 0)
+    for eng in ENGINES:
+        same(ix.search_range(Q, radius, cap, flat_engine=eng), want, "%s staging=%r" % (eng, staging))
+        assert ix.stats()["overflow_queries"] == over, (eng, staging)
+    ix.close()
+
+
 # ---- 2. the continuous table: range_ref under the 5 % cap, distances bit-equal to a flat search's
 @pytest.fixture(scope="module")
 def cont():

@@ -1,0 +1,293 @@
+// The C ABI of libepsilla_gfx950 (include/epsilla_gfx950.h): argument checks, dispatch to IndexBase / Index, and no exception across it.
+#include "index.hpp"
+
+#include <cstdio>
+#include <new>
+#include <string>
+
+using eps::Index;
+using eps::IndexBase;
+
+// No C++ exception crosses the C ABI: allocation failures and anything else thrown below map to the reference's
+// status codes (utils/error.hpp:11-41) with the text in eps_index_last_error.
+static int32_t map_exception(IndexBase* ix) {
+  try {
+    throw;
+  } catch (const std::bad_alloc&) {
+    return ix ? ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "out of host memory") : EPS_INFRA_UNEXPECTED_ERROR;
+  } catch (const std::exception& e) {
+    return ix ? ix->fail(EPS_DB_UNEXPECTED_ERROR, std::string("unexpected: ") + e.what()) : EPS_DB_UNEXPECTED_ERROR;
+  } catch (...) {
+    return ix ? ix->fail(EPS_DB_UNEXPECTED_ERROR, "unexpected exception") : EPS_DB_UNEXPECTED_ERROR;
+  }
+}
+#define IX(h) reinterpret_cast<IndexBase*>(h)
+#define CIX(h) reinterpret_cast<const IndexBase*>(h)
+#define GUARD(h, expr)             \
+  do {                             \
+    if (!(h)) return EPS_USER_ERROR; \
+    try {                          \
+      return (expr);               \
+    } catch (...) {                \
+      return map_exception(IX(h)); \
+    }                              \
+  } while (0)
+// The entries that only a single-device index serves: `f(Index&)` runs with the index's device current; a sharded handle is refused with the
+// entry's own text and error class.
+template <class F>
+static int32_t on_single_device(eps_index* h, const char* refusal, int32_t err_class, F&& f) {
+  if (!h) return EPS_USER_ERROR;
+  Index* ix = dynamic_cast<Index*>(IX(h));
+  if (!ix) return IX(h)->fail(EPS_DB_UNSUPPORTED_ERROR, refusal, err_class);
+  try {
+    if (hipSetDevice(ix->device_) != hipSuccess) return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");
+    return f(*ix);
+  } catch (...) {
+    return map_exception(ix);
+  }
+}
+
+extern "C" {
+
+void eps_default_search_params(eps_search_params* p) {
+  if (!p) return;
+  p->mode = EPS_MODE_REFERENCE;
+  p->flat_engine = EPS_FLAT_AUTO;
+  p->prefilter = 0;         // Config::PreFilter{false}
+  p->intra_threads = 4;     // Config::IntraQueryThreads{4}      (config/config.hpp:18)
+  p->master_queue = 500;    // Config::MasterQueueSize{500}      (:19)
+  p->local_queue = 500;     // Config::LocalQueueSize{500}       (:20)
+  p->sync_interval = 15;    // Config::GlobalSyncInterval{15}    (:21)
+  p->filter_in_traversal = 0;
+  p->reserved = 0;
+}
+
+void eps_default_build_params(eps_build_params* p) {
+  if (!p) return;
+  p->search_length = 45;  // NSGConfig(45, 50, 300, 100), db/ann_graph_segment.cpp:29
+  p->out_degree = 50;
+  p->candidate_pool_size = 300;
+  p->knng = 100;
+  p->seed = 100;  // nsg.cpp:19
+  p->reserved = 0;
+}
+
+int32_t eps_index_create(int64_t dim, int32_t metric, int32_t device, eps_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (dim <= 0 || dim > 8192 || metric < 0 || metric > 2) return EPS_USER_ERROR;  // one query must fit in LDS next to the queues
+  try {
+    Index* ix = new Index(dim, metric, device);
+    const int32_t rc = ix->init();
+    if (rc != EPS_OK) {
+      std::fprintf(stderr, "eps_index_create: %s\n", ix->last_error());
+      delete ix;
+      return rc;
+    }
+    *out = reinterpret_cast<eps_index*>(static_cast<IndexBase*>(ix));
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_index_create_sharded(int64_t dim, int32_t metric, const int32_t* devices, int32_t shards, eps_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (dim <= 0 || dim > 8192 || metric < 0 || metric > 2 || !devices || shards <= 0 || shards > 16) return EPS_USER_ERROR;
+  try {
+    std::string err;
+    IndexBase* g = eps::make_shard_group(dim, metric, devices, shards, &err);
+    if (!g) {
+      std::fprintf(stderr, "eps_index_create_sharded: %s\n", err.c_str());
+      return EPS_INFRA_UNEXPECTED_ERROR;
+    }
+    *out = reinterpret_cast<eps_index*>(g);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_index_destroy(eps_index* h) {
+  try {
+    delete reinterpret_cast<IndexBase*>(h);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+const char* eps_index_last_error(const eps_index* h) { return h ? CIX(h)->last_error() : "null handle"; }
+int32_t eps_index_last_error_class(const eps_index* h) { return h ? CIX(h)->last_error_class() : EPS_ERRCLASS_OTHER; }
+int32_t eps_index_set_stream(eps_index* h, void* s) { GUARD(h, IX(h)->set_stream(s)); }
+int32_t eps_index_synchronize(eps_index* h) { GUARD(h, IX(h)->synchronize()); }
+int32_t eps_index_attach_rows(eps_index* h, const float* rows, int64_t n) { GUARD(h, IX(h)->attach_rows(rows, n)); }
+int32_t eps_index_append_rows(eps_index* h, const float* rows, int64_t n) { GUARD(h, IX(h)->append_rows(rows, n)); }
+int32_t eps_index_attach_shard_rows(eps_index* h, int32_t shard, const float* rows, int64_t n_local) { GUARD(h, IX(h)->attach_shard_rows(shard, rows, n_local)); }
+int32_t eps_index_clone_rows(eps_index* dst, eps_index* src, int64_t n) {
+  if (!src) return EPS_USER_ERROR;
+  GUARD(dst, IX(dst)->clone_rows(*IX(src), n));
+}
+int64_t eps_index_row_count(const eps_index* h) { return h ? CIX(h)->row_count() : -1; }
+int32_t eps_index_set_id_map(eps_index* h, int64_t b, int64_t s) { GUARD(h, IX(h)->set_id_map(b, s)); }
+int32_t eps_index_set_deleted(eps_index* h, const uint8_t* bits, int64_t nbytes) { GUARD(h, IX(h)->set_deleted(bits, nbytes)); }
+int32_t eps_index_set_int_filter(eps_index* h, const void* col, int64_t stride, int32_t width, int32_t op, int64_t c) {
+  GUARD(h, IX(h)->set_int_filter(col, stride, width, op, c));
+}
+int32_t eps_index_set_filter_program(eps_index* h, const eps_filter_op* ops, int32_t nops, const void* rows, int64_t stride, int64_t n_rows) {
+  GUARD(h, IX(h)->set_filter_program(ops, nops, rows, stride, n_rows, 0));
+}
+int32_t eps_index_set_filter_program_ex(eps_index* h, const eps_filter_op* ops, int32_t nops, const void* rows, int64_t stride, int64_t n_rows,
+                                        int32_t flags) {
+  GUARD(h, IX(h)->set_filter_program(ops, nops, rows, stride, n_rows, flags));
+}
+int32_t eps_index_search_walk(eps_index* h, const float* q, int64_t nq, int32_t limit, int32_t cap, const eps_search_params* p, int64_t* ids,
+                              float* dist, int32_t* counts) {
+  if (limit <= 0 || cap < limit) return EPS_USER_ERROR;
+  GUARD(h, IX(h)->search(q, nq, cap, p, ids, dist, counts, limit));
+}
+int32_t eps_index_select_edges(eps_index* h, const int64_t* nodes, int64_t m, const int64_t* cands, int32_t cands_per_node, int32_t depth,
+                               int32_t out_degree, int64_t* out_ids, int32_t* out_deg) {
+  return on_single_device(h, "select_edges: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    return eps::select_edges(ix, nodes, m, cands, cands_per_node, depth, out_degree, out_ids, out_deg);
+  });
+}
+int32_t eps_index_inter_insert(eps_index* h, const int64_t* ids, const int32_t* deg, int64_t n, int32_t out_degree, int64_t* out_ids,
+                               int32_t* out_deg) {
+  return on_single_device(h, "inter_insert: single-device indices only", EPS_ERRCLASS_OTHER,
+                          [&](Index& ix) { return eps::inter_insert(ix, ids, deg, n, out_degree, out_ids, out_deg); });
+}
+int32_t eps_index_knn_graph(eps_index* h, int64_t n, const eps_build_params* p, int64_t* out_ids) {
+  if (!out_ids) return EPS_USER_ERROR;
+  return on_single_device(h, "knn_graph: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    if (n < 2 || n > ix.row_count()) return ix.fail(EPS_USER_ERROR, "knn_graph: n must be in [2, rows]");
+    eps::BuildStage st;
+    st.stop_after = 1;
+    st.out_ids = out_ids;
+    return eps::graph_build(ix, n, eps::build_params_or_default(p), &st);
+  });
+}
+int32_t eps_index_link(eps_index* h, int64_t n, const int64_t* knn, int64_t navigation_point, const eps_build_params* p, int64_t* out_ids,
+                       int32_t* out_deg, int64_t* nav_out) {
+  if (!out_ids || !out_deg) return EPS_USER_ERROR;
+  return on_single_device(h, "link: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    if (n < 2 || n > ix.row_count()) return ix.fail(EPS_USER_ERROR, "link: n must be in [2, rows]");
+    eps::BuildStage st;
+    st.knn_in = knn;
+    st.nav_in = navigation_point;
+    st.stop_after = 2;
+    st.out_ids = out_ids;
+    st.out_deg = out_deg;
+    st.nav_out = nav_out;
+    return eps::graph_build(ix, n, eps::build_params_or_default(p), &st);
+  });
+}
+int32_t eps_index_mirror_view(eps_index* h, int32_t bits, const float* queries, int64_t nq, eps_mirror_view* view) {
+  if (!view) return EPS_USER_ERROR;
+  return on_single_device(h, "mirror_view: single-device indices only", EPS_ERRCLASS_OTHER,
+                          [&](Index& ix) { return eps::flat_mirror_view(ix, bits, queries, nq, view); });
+}
+int32_t eps_index_filter_pass(eps_index* h, const float* queries, int64_t nq, int32_t bits, int64_t row_lo, int64_t row_hi, int64_t cap, int32_t mode,
+                              int32_t thr_form, const void* thr, void* T_out, uint32_t* cnt_out, void* cand_out) {
+  return on_single_device(h, "filter_pass: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    return eps::flat_filter_pass(ix, queries, nq, bits, row_lo, row_hi, cap, mode, thr_form, thr, T_out, cnt_out, cand_out);
+  });
+}
+int32_t eps_index_load_table(eps_index* h, const char* path, const eps_table_layout* layout, int64_t* n_out) {
+  return on_single_device(h, "load_table: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) { return ix.load_table(path, layout, n_out); });
+}
+int32_t eps_index_build(eps_index* h, int64_t n, const eps_build_params* p) { GUARD(h, IX(h)->build(n, p)); }
+int32_t eps_index_set_graph(eps_index* h, int64_t n, const int64_t* off, const int64_t* nbr, int64_t nav) {
+  GUARD(h, IX(h)->set_graph(n, off, nbr, nav));
+}
+int32_t eps_index_graph_info(const eps_index* h, int64_t* n, int64_t* e, int64_t* nav) { return h ? CIX(h)->graph_info(n, e, nav) : EPS_USER_ERROR; }
+int32_t eps_index_get_graph(const eps_index* h, int64_t* off, int64_t* nbr) { return h ? CIX(h)->get_graph(off, nbr) : EPS_USER_ERROR; }
+int32_t eps_index_save_graph(eps_index* h, const char* path) { GUARD(h, IX(h)->save_graph(path)); }
+int32_t eps_index_load_graph(eps_index* h, const char* path) { GUARD(h, IX(h)->load_graph(path)); }
+int32_t eps_index_search(eps_index* h, const float* q, int64_t nq, int32_t k, const eps_search_params* p, int64_t* ids,
+                         float* dist, int32_t* counts) {
+  GUARD(h, IX(h)->search(q, nq, k, p, ids, dist, counts));
+}
+int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out) {
+  return on_single_device(h, "select: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
+                          [&](Index& ix) { return ix.select(skip, limit, ids_out, count_out, total_out); });
+}
+int32_t eps_index_search_range(eps_index* h, const float* q, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p, int64_t* ids,
+                               float* dist, int32_t* counts, int64_t* totals) {
+  return on_single_device(h, "search_range: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
+                          [&](Index& ix) { return ix.search_range(q, nq, radius, cap, p, ids, dist, counts, totals); });
+}
+int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out) {
+  if (!h || !out) return EPS_USER_ERROR;
+  return const_cast<IndexBase*>(CIX(h))->last_stats(out);
+}
+int32_t eps_index_kernel_times(eps_index* h, double* ms_out, int32_t cap) { return h ? IX(h)->kernel_times(ms_out, cap) : 0; }
+
+int32_t eps_normalize_rows(float* rows, int64_t n, int64_t dim, int32_t only_if_nonzero, int32_t device, void* stream) {
+  if (n < 0 || dim <= 0 || (n > 0 && !rows)) return EPS_USER_ERROR;
+  if (n == 0) return EPS_OK;
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (eps::is_device_ptr(rows)) {
+    eps::launch_normalize(rows, n, (int)dim, only_if_nonzero != 0, s);
+    return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+  }
+  float* d = nullptr;
+  const size_t bytes = (size_t)n * dim * sizeof(float);
+  if (hipMalloc(&d, bytes) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  bool ok = hipMemcpyAsync(d, rows, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (ok) eps::launch_normalize(d, n, (int)dim, only_if_nonzero != 0, s);
+  ok = ok && hipMemcpyAsync(rows, d, bytes, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  (void)hipFree(d);
+  return ok ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+int32_t eps_merge_topk(const float* dist, const int64_t* ids, int32_t shards, int64_t nq, int32_t k, float* out_dist,
+                       int64_t* out_ids, int32_t device, void* stream) {
+  if (!dist || !ids || !out_dist || !out_ids || shards <= 0 || shards > 16 || nq < 0 || k <= 0) return EPS_USER_ERROR;
+  if (nq == 0) return EPS_OK;
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool dev = eps::is_device_ptr(dist);
+  if (dev != eps::is_device_ptr(ids) || dev != eps::is_device_ptr(out_dist) || dev != eps::is_device_ptr(out_ids)) return EPS_USER_ERROR;
+  if (dev) {
+    eps::launch_merge_shards(dist, ids, shards, nq, k, out_dist, out_ids, s);
+    return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+  }
+  const size_t in_n = (size_t)shards * nq * k, out_n = (size_t)nq * k;
+  char* d = nullptr;
+  if (hipMalloc(&d, in_n * 12 + out_n * 12 + 64) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  int64_t* d_ids = reinterpret_cast<int64_t*>(d);
+  int64_t* d_oids = d_ids + in_n;
+  float* d_dist = reinterpret_cast<float*>(d_oids + out_n);
+  float* d_odist = d_dist + in_n;
+  bool ok = hipMemcpyAsync(d_ids, ids, in_n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+            hipMemcpyAsync(d_dist, dist, in_n * 4, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (ok) eps::launch_merge_shards(d_dist, d_ids, shards, nq, k, d_odist, d_oids, s);
+  ok = ok && hipMemcpyAsync(out_ids, d_oids, out_n * 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
+       hipMemcpyAsync(out_dist, d_odist, out_n * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+       hipStreamSynchronize(s) == hipSuccess;
+  (void)hipFree(d);
+  return ok ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+// the same merge over ONE gathered buffer: shard s contributed `shard_stride_bytes` bytes holding int64 ids[nq][k] at
+// offset 0 and float dist[nq][k] at `dist_offset_bytes` (what a single all-gather of a packed per-rank buffer delivers)
+int32_t eps_merge_topk_packed(const void* gathered, int64_t shard_stride_bytes, int64_t dist_offset_bytes, int32_t shards, int64_t nq,
+                              int32_t k, float* out_dist, int64_t* out_ids, int32_t device, void* stream) {
+  if (!gathered || !out_dist || !out_ids || shards <= 0 || shards > 16 || nq < 0 || k <= 0) return EPS_USER_ERROR;
+  if (shard_stride_bytes < dist_offset_bytes + nq * k * 4 || dist_offset_bytes < nq * k * 8 || (dist_offset_bytes & 3) || (shard_stride_bytes & 7))
+    return EPS_USER_ERROR;
+  if (nq == 0) return EPS_OK;
+  if (!eps::is_device_ptr(gathered) || !eps::is_device_ptr(out_dist) || !eps::is_device_ptr(out_ids)) return EPS_USER_ERROR;
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  const char* base = static_cast<const char*>(gathered);
+  eps::launch_merge_shards(reinterpret_cast<const float*>(base + dist_offset_bytes), reinterpret_cast<const int64_t*>(base), shards, nq, k,
+                           out_dist, out_ids, static_cast<hipStream_t>(stream), shard_stride_bytes);
+  return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+int32_t eps_set_tuning(const char* name, const char* value) {
+  eps::tune_set(name, value);
+  return EPS_OK;
+}
+
+}  // extern "C"

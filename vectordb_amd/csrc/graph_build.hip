@@ -507,7 +507,7 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
           launch_rerank(ra, s);
         }
       } else {
-        rc = ix.flat_stream(dq, nq, k1, 0, n, run.as<u64>(), false, -1, false);
+        rc = ix.flat_stream(dq, nq, k1, 0, n, run.as<u64>(), -1, false);
       }
       if (rc != EPS_OK) {
         ix.scan_limit_ = -1;
@@ -537,7 +537,7 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
     hipLaunchKernelGGL(centroid_kernel, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, s, ix.d_rows_, n, dim, rpb, cen.as<float>());
     hipLaunchKernelGGL(scale_kernel, dim3((dim + 255) / 256), dim3(256), 0, s, cen.as<float>(), dim, 1.0f / (float)n);
   }
-  int32_t rc = ix.flat_stream(cen.as<float>(), 1, 1, 0, n, run.as<u64>(), false, 0, false);
+  int32_t rc = ix.flat_stream(cen.as<float>(), 1, 1, 0, n, run.as<u64>(), 0, false);
   if (rc != EPS_OK) return rc;
   u64 navkey = 0;
   HIPCHK(hipMemcpyAsync(&navkey, run.p, 8, hipMemcpyDeviceToHost, s));

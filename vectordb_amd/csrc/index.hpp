@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,9 @@ struct DevBuf {  // growable device allocation
   ~DevBuf();
   // returns false on allocation failure
   bool reserve(size_t bytes);
+  // a new allocation of `want` bytes (sized as reserve sizes it) whose first `keep` bytes are the old one's, complete when this returns;
+  // hipErrorOutOfMemory: nothing changed
+  hipError_t grow_keeping(size_t want, size_t keep, hipStream_t s);
   void release();
   template <class T>
   T* as() const { return static_cast<T*>(p); }
@@ -69,6 +73,7 @@ size_t scratch_reclaim();   // bytes released
 const char* tune_env(const char* name);
 // the integer value of a switch, read ONCE (a second lookup may find the entry gone: eps_set_tuning is a process-wide runtime call), or `dflt`
 int tune_int(const char* name, int dflt);
+void tune_set(const char* name, const char* value);   // eps_set_tuning: value null removes the entry, name null empties the table
 
 struct BuildStage;   // stage-level entry of the graph build (below)
 struct Quant8View {   // the table's 8-bit mirror as other kernels see it (mirror_build.hip)
@@ -139,7 +144,6 @@ class Index : public IndexBase {
     return attach_rows(rows, n_local);
   }
   int32_t clone_rows(IndexBase& src, int64_t n) override;
-  const float* device_rows() const { return d_rows_; }
   // rows of a strided host table: row i at rows + i*pitch_floats (hash-sharded tables: pitch = shards*dim)
   int32_t attach_rows_strided(const float* rows, int64_t n, int64_t pitch_floats, bool copy_device_rows = false);
   int32_t append_rows_strided(const float* rows, int64_t n_new, int64_t pitch_floats);
@@ -169,12 +173,10 @@ class Index : public IndexBase {
                        int32_t* counts_out, int64_t* totals_out);
 
   int64_t row_count() const override { return n_rows_; }
-  const eps_search_stats& stats() const { return stats_; }
 
   // ---- used by the engine translation units
   int32_t hip_fail(hipError_t e, const char* what);
   FilterSpec filter_spec() const;
-  hipStream_t stream() const { return stream_; }
 
   int64_t dim_;
   int metric_;
@@ -211,7 +213,6 @@ class Index : public IndexBase {
   int64_t prog_stride_ = 0, prog_rows_n_ = 0;
   int32_t prog_len_ = 0;
   bool prog_uses_dist_ = false;
-  int32_t walk_limit_ = 0;            // of the search call in progress
   bool prefilter_call_ = false;
 
   // graph (reference layout kept on the host for get/save; device form in GraphDev)
@@ -254,21 +255,39 @@ class Index : public IndexBase {
   int64_t fcol_rows_ = 0;       // rows the attribute column behind d_fcol_ covers
 
   eps_search_stats stats_{};
-  // set by search() around a matrix-engine call: what the engine launches right before its final host sync (the result conversion),
-  // so that the device works through the round trip; only called when the batch is one slice
-  std::function<void()> pre_sync_;
-  bool result_finalized_ = false;   // the conversion has run on the CURRENT contents of the result keys (an engine that rewrites them clears it)
-  int64_t pre_sync_nq_ = -1;   // queries of the call that set it (a batch run in slices converts after the last slice instead)
-  // ... and where that conversion writes: the matrix engine's last re-rank does it itself (RerankArgs::fin_*) instead of a launch
-  int64_t* fin_ids_ = nullptr;
-  float* fin_dist_ = nullptr;
-  int32_t* fin_cnt_ = nullptr;
+  // what search() publishes to the matrix engine for the length of one call (cleared by `call_ = {}` on every way out of it)
+  struct CallCtx {
+    // what the engine launches right before its final host sync (the result conversion), so that the device works through the round trip;
+    // only called when the batch is one slice
+    std::function<void()> pre_sync;
+    int64_t nq = -1;   // queries of the call that set it (a batch run in slices converts after the last slice instead)
+    // ... and where that conversion writes: the matrix engine's last re-rank does it itself (RerankArgs::fin_*) instead of a launch
+    int64_t* fin_ids = nullptr;
+    float* fin_dist = nullptr;
+    int32_t* fin_cnt = nullptr;
+  } call_;
+  // the conversion has run on the CURRENT contents of the result keys (an engine that rewrites them clears it).  Not part of call_: search()
+  // reads it after the engine has returned and call_ is cleared
+  bool result_finalized_ = false;
 
  private:
-  int32_t flat_stream(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys,
-                      bool merge_run, int metric = -1, bool filtered = true);
-  int32_t flat_stream_page(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, bool merge_run, int metric,
-                           bool filtered, const u64* lo, int64_t lo_stride);
+  int32_t flat_stream(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric = -1, bool filtered = true);
+  int32_t flat_stream_page(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric, bool filtered,
+                           const u64* lo, int64_t lo_stride);
+  // ---- the steps search, select and search_range share (index_calls.cpp)
+  // refuses a deleted bitset / filter column / filter program's rows that an append has left shorter than the table
+  int32_t check_filters_cover_table(const char* who);
+  // a call that reports statistics and takes a slot of the kernel ring (select takes neither: it leaves no trace)
+  void begin_timed_call();
+  void end_timed_call();   // the slot counts only when a main kernel ran
+  // *dq = queries where they are on the device already, else their upload in q_buf_
+  int32_t stage_queries(const char* who, const float* queries, int64_t nq, const float** dq);
+  // one device block of results to up to four host arrays: part i is `bytes` bytes at `off` of the block (dst null: not asked for)
+  struct HostPart {
+    void* dst;
+    size_t off, bytes;
+  };
+  int32_t fetch_to_host(const void* d_block, size_t block_bytes, std::initializer_list<HostPart> parts);
   friend int32_t quant8_view(Index&, Quant8View*);
   friend void quant8_queries(Index&, const Quant8View&, const float*, int64_t, signed char*, float*);
   friend int32_t flat_mfma_search(Index&, const float*, int64_t, int, u64*, bool, int);
@@ -320,6 +339,19 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
 int32_t inter_insert(Index& ix, const int64_t* ids, const int32_t* deg, int64_t n, int32_t R, int64_t* out_ids, int32_t* out_deg);
 
 bool is_device_ptr(const void* p);
+
+inline eps_build_params build_params_or_default(const eps_build_params* p) {
+  eps_build_params bp;
+  if (p) bp = *p; else eps_default_build_params(&bp);
+  return bp;
+}
+
+// for member functions of Index that return a status
+#define HIP_TRY(expr)                                  \
+  do {                                                 \
+    hipError_t e__ = (expr);                           \
+    if (e__ != hipSuccess) return hip_fail(e__, #expr); \
+  } while (0)
 
 // hash-sharded table over several devices of one process (shard_group.cpp)
 IndexBase* make_shard_group(int64_t dim, int metric, const int32_t* devices, int32_t shards, std::string* err);

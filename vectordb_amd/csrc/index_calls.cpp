@@ -1,0 +1,506 @@
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, the steps they share, and the read-out of their statistics.
+#include "index.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+namespace eps {
+
+// ------------------------------------------------------------------------------------------------ the exact stream engine
+int32_t Index::flat_stream(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric, bool filtered) {
+  if (k <= 1024) return flat_stream_page(dq, nq, k, row_begin, row_end, run_keys, metric, filtered, nullptr, 0);
+  // More than 1024 results per query (the reference's BruteForceSearch has no cap: it sorts all n candidates,
+  // vec_search_executor.cpp:756-767): pages of 1024 - page p is the scan's 1024 best keys ordered AFTER the last key of page
+  // p-1 ((dist, id) keys are unique per row, so the pages are disjoint and their concatenation is the sorted answer).
+  if (!page_buf_.reserve((size_t)nq * 1024 * sizeof(u64))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (result page)");
+  for (int done = 0; done < k; done += 1024) {
+    const int kc = std::min(1024, k - done);
+    const int32_t rc = flat_stream_page(dq, nq, kc, row_begin, row_end, page_buf_.as<u64>(), metric, filtered, done ? run_keys + (done - 1) : nullptr, k);
+    if (rc != EPS_OK) return rc;
+    HIP_TRY(hipMemcpy2DAsync(run_keys + done, (size_t)k * sizeof(u64), page_buf_.p, (size_t)kc * sizeof(u64), (size_t)kc * sizeof(u64), (size_t)nq,
+                             hipMemcpyDeviceToDevice, stream_));
+  }
+  return EPS_OK;
+}
+
+int32_t Index::flat_stream_page(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric, bool filtered,
+                                const u64* lo, int64_t lo_stride) {
+  if (row_end <= row_begin) {
+    launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
+    return EPS_OK;
+  }
+  const int W = flat_scan_waves(row_end - row_begin, nq, (int)dim_);
+  if (!partial_buf_.reserve((size_t)nq * W * k * sizeof(u64))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (partial lists)");
+  FlatScanArgs a;
+  a.rows = d_rows_;
+  a.row_begin = row_begin;
+  a.row_end = row_end;
+  a.dim = (int)dim_;
+  a.metric = metric < 0 ? metric_ : metric;
+  a.queries = dq;
+  a.nq = nq;
+  a.k = k;
+  a.f = filter_spec();
+  if (!filtered) a.f = no_filter();
+  a.partial = partial_buf_.as<u64>();
+  a.W = W;
+  a.thr_in = nullptr;
+  a.lo_in = lo;
+  a.lo_stride = lo_stride;
+  HIP_TRY(hipEventRecord(evk0_, stream_));
+  launch_flat_scan(a, stream_);
+  HIP_TRY(hipEventRecord(evk1_, stream_));
+  launch_merge_lists(a.partial, W * k, k, nq, run_keys, false, stream_);
+  HIP_TRY(hipGetLastError());
+  stats_.main_kernel_launches += 1;
+  stats_.main_kernel_rows = row_end - row_begin;
+  stats_.main_kernel_queries = nq;
+  stats_.main_kernel_bits = 32;
+  stats_.dist_evals += nq * (row_end - row_begin);
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the steps the calls share
+int32_t Index::check_filters_cover_table(const char* who) {
+  if (d_deleted_ && deleted_bytes_ < (n_rows_ + 7) / 8)
+    return fail(EPS_USER_ERROR, std::string(who) + ": the deleted bitset is shorter than the table (rows were appended): call set_deleted again");
+  if (f_op_ && d_fcol_ && fcol_rows_ < n_rows_)
+    return fail(EPS_USER_ERROR, std::string(who) + ": the filter column is shorter than the table (rows were appended): call set_int_filter again");
+  if (prog_len_ > 0 && prog_rows_n_ < n_rows_)
+    return fail(EPS_USER_ERROR, std::string(who) + ": the filter program's attribute rows are shorter than the table (rows were appended): call set_filter_program again");
+  return EPS_OK;
+}
+
+void Index::begin_timed_call() {
+  std::memset(&stats_, 0, sizeof(stats_));
+  stage_n_ = 0;
+  kring_seq_ += 1;
+  const int slot = (int)(kring_seq_ % KRING);
+  evk0_ = kring_[slot][0];
+  evk1_ = kring_[slot][1];
+  kring_valid_[slot] = false;
+}
+void Index::end_timed_call() { kring_valid_[kring_seq_ % KRING] = stats_.main_kernel_launches > 0; }
+
+int32_t Index::stage_queries(const char* who, const float* queries, int64_t nq, const float** dq) {
+  *dq = queries;
+  if (is_device_ptr(queries)) return EPS_OK;
+  const size_t qb = (size_t)nq * dim_ * sizeof(float);
+  if (!q_buf_.reserve(qb)) return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of device memory (queries)");
+  const bool staging = !(tune_int("EPS_HOST_STAGING", 1) == 0);   // (A/B switch)
+  if (staging && qb <= ((size_t)256 << 10) && h_q_.reserve(qb)) {   // (a few vectors: -30 us per call; a 3 MB batch: the runtime's pageable path measured faster than memcpy + DMA)
+    // (the previous call's copy out of h_q_ has completed: every call with host queries ends in a stream sync or its results are device-side and
+    // the caller orders the stream; a second call on the same index may not start before the first returns - one mutex per index)
+    HIP_TRY(hipStreamSynchronize(stream_));
+    memcpy(h_q_.p, queries, qb);
+    HIP_TRY(hipMemcpyAsync(q_buf_.p, h_q_.p, qb, hipMemcpyHostToDevice, stream_));
+  } else {
+    HIP_TRY(hipMemcpyAsync(q_buf_.p, queries, qb, hipMemcpyHostToDevice, stream_));
+  }
+  *dq = q_buf_.as<float>();
+  return EPS_OK;
+}
+
+int32_t Index::fetch_to_host(const void* d_block, size_t block_bytes, std::initializer_list<HostPart> parts) {
+  if (!(tune_int("EPS_HOST_STAGING", 1) == 0) && h_out_.reserve(block_bytes)) {   // one copy into page-locked memory, split on the host
+    HIP_TRY(hipMemcpyAsync(h_out_.p, d_block, block_bytes, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    for (const HostPart& part : parts)
+      if (part.dst) memcpy(part.dst, static_cast<const char*>(h_out_.p) + part.off, part.bytes);
+  } else {   // (no page-locked memory to be had: the pageable copies)
+    for (const HostPart& part : parts)
+      if (part.dst) HIP_TRY(hipMemcpyAsync(part.dst, static_cast<const char*>(d_block) + part.off, part.bytes, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+  }
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ search
+int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_search_params* pp, int64_t* ids,
+                      float* dist, int32_t* counts, int32_t walk_limit) {
+  eps_search_params p;
+  if (pp) p = *pp; else eps_default_search_params(&p);
+  prefilter_call_ = p.prefilter != 0;
+  if (nq < 0 || k <= 0) return fail(EPS_USER_ERROR, "search: nq must be >= 0 and k > 0");
+  if (nq == 0) return EPS_OK;
+  if (!queries || !ids || !dist) return fail(EPS_USER_ERROR, "search: null buffer");
+  if (k > (1 << 20)) return fail(EPS_DB_UNSUPPORTED_ERROR, "search: k > 1048576 is not supported");
+  if (p.master_queue <= 0 || p.local_queue <= 0 || p.sync_interval <= 0 || p.intra_threads <= 0)
+    return fail(EPS_USER_ERROR, "search: queue sizes, sync interval and thread count must be positive");
+  HIP_TRY(hipSetDevice(device_));
+  begin_timed_call();
+  int32_t rc = check_filters_cover_table("search");
+  if (rc != EPS_OK) return rc;
+
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)))
+    return fail(EPS_USER_ERROR, "search: ids_out, dist_out and counts_out must all be host or all be device pointers");
+
+  const float* dq;
+  rc = stage_queries("search", queries, nq, &dq);
+  if (rc != EPS_OK) return rc;
+
+  // mode selection of VecSearchExecutor::Search (vec_search_executor.cpp:855-935)
+  int mode = p.mode;
+  bool cap_local = false;
+  if (mode == EPS_MODE_REFERENCE) {
+    if (p.prefilter) {
+      mode = EPS_MODE_FLAT;
+    } else if (n_indexed_ < 512) {  // BruteforceThreshold, vec_search_executor.hpp:28
+      mode = EPS_MODE_FLAT;
+      cap_local = walk_limit == 0;  // result_size = min(size, limit, L_local_)  (:864); a candidate walk is cut by its caller
+    } else {
+      mode = EPS_MODE_GRAPH;
+    }
+  }
+  if (mode == EPS_MODE_GRAPH && n_indexed_ <= 0) return fail(EPS_USER_ERROR, "search: graph mode requested but no graph is set");
+
+  if (!run_buf_.reserve((size_t)nq * k * sizeof(u64))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (results)");
+  u64* run_keys = run_buf_.as<u64>();
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  // results out (decided before the engines run: the matrix engine launches the result conversion itself, in front of its final
+  // host sync, so that the device does not idle through that round trip)
+  int64_t* d_ids = ids;
+  float* d_dist = dist;
+  int32_t* d_cnt = counts;
+  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float), out_bytes = ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
+  if (!out_dev) {
+    if (!out_buf_.reserve(out_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (outputs)");
+    d_ids = out_buf_.as<int64_t>();
+    d_dist = reinterpret_cast<float*>(out_buf_.as<char>() + ids_bytes);
+    d_cnt = reinterpret_cast<int32_t*>(out_buf_.as<char>() + ids_bytes + dist_bytes);
+  }
+  result_finalized_ = false;
+  auto finalize = [&]() {
+    launch_finalize(run_keys, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
+    (void)hipEventRecord(ev1_, stream_);
+    result_finalized_ = true;
+  };
+
+  int keff = k;
+  if (mode == EPS_MODE_FLAT) {
+    if (cap_local && p.local_queue < keff) keff = (int)p.local_queue;
+    if (keff < k) launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
+    int engine = p.flat_engine;
+    if (engine < EPS_FLAT_AUTO || engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search: unknown flat engine");
+    int bits = engine == EPS_FLAT_MFMA ? 16 : (engine == EPS_FLAT_MFMA_I8 ? 8 : 0);   // AUTO: the library picks the operand width too
+    if (engine == EPS_FLAT_MFMA_I8) engine = EPS_FLAT_MFMA;
+    if (engine == EPS_FLAT_AUTO) engine = flat_mfma_profitable(*this, nq, keff) ? EPS_FLAT_MFMA : EPS_FLAT_STREAM;
+    // a filter on @distance needs exact distances wherever it is evaluated; the MFMA engine selects its seeds on
+    // approximate keys, so such searches stay on the exact stream engine
+    if (prog_len_ > 0 && prog_uses_dist_ && !prefilter_call_) engine = EPS_FLAT_STREAM;
+    if (keff > 1024) engine = EPS_FLAT_STREAM;   // result pages (see flat_stream)
+    if (keff == k) {
+      if (engine == EPS_FLAT_MFMA) {
+        // (called by the engine in front of its final sync; again after a fall-back pass.  The callable captures locals of this
+        // frame: the guard clears it on every way out, an exception from the engine included)
+        struct CallGuard {
+          Index& ix;
+          ~CallGuard() { ix.call_ = {}; }
+        } guard{*this};
+        call_ = CallCtx{finalize, nq, d_ids, d_dist, d_cnt};
+        rc = flat_mfma_search(*this, dq, nq, k, run_keys, false, bits);
+      } else {
+        rc = flat_stream(dq, nq, k, 0, n_rows_, run_keys);
+      }
+    } else {
+      // narrower result (L_local cap): compute into a k_eff-wide list, then widen
+      if (!tmp_buf_.reserve((size_t)nq * keff * sizeof(u64))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory");
+      u64* narrow = tmp_buf_.as<u64>();
+      rc = engine == EPS_FLAT_MFMA ? flat_mfma_search(*this, dq, nq, keff, narrow, false, bits)
+                                   : flat_stream(dq, nq, keff, 0, n_rows_, narrow);
+      if (rc == EPS_OK)
+        HIP_TRY(hipMemcpy2DAsync(run_keys, (size_t)k * sizeof(u64), narrow, (size_t)keff * sizeof(u64),
+                                 (size_t)keff * sizeof(u64), (size_t)nq, hipMemcpyDeviceToDevice, stream_));
+    }
+    if (rc != EPS_OK) return rc;
+  } else {
+    int64_t evals = 0;
+    rc = graph_search(*this, dq, nq, k, p, run_keys, &evals, walk_limit);
+    if (rc != EPS_OK) return rc;
+  }
+
+  if (!result_finalized_) finalize();
+  if (!out_dev) {
+    rc = fetch_to_host(d_ids, out_bytes, {{ids, 0, ids_bytes}, {dist, ids_bytes, dist_bytes}, {counts, ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ select
+// SearchByAttribute's full-scan branch (vec_search_executor.cpp:1016-1029).  Touches nothing a search reads: no statistics, no event of the
+// kernel ring, no engine state - only scratch of its own.
+int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* count_out, int64_t* total_out) {
+  if (skip < 0 || limit < 0) return fail(EPS_USER_ERROR, "select: skip and limit must be >= 0");
+  if (!count_out || (limit > 0 && n_rows_ > 0 && !ids_out)) return fail(EPS_USER_ERROR, "select: null buffer");
+  HIP_TRY(hipSetDevice(device_));
+  const int32_t rc = check_filters_cover_table("select");
+  if (rc != EPS_OK) return rc;
+  const int64_t n = n_rows_;
+  const bool out_dev = is_device_ptr(count_out);
+  if ((limit > 0 && n > 0 && out_dev != is_device_ptr(ids_out)) || (total_out && out_dev != is_device_ptr(total_out)))
+    return fail(EPS_USER_ERROR, "select: ids_out, count_out and total_out must all be host or all be device pointers");
+  if (n == 0) {   // an empty table: nothing to judge
+    if (out_dev) {
+      HIP_TRY(hipMemsetAsync(count_out, 0, sizeof(int64_t), stream_));
+      if (total_out) HIP_TRY(hipMemsetAsync(total_out, 0, sizeof(int64_t), stream_));
+    } else {
+      *count_out = 0;
+      if (total_out) *total_out = 0;
+    }
+    return EPS_OK;
+  }
+  SelectArgs a;
+  a.f = filter_spec();
+  a.f.prog_use_dist = 0;   // LogicalEvaluate(root, id): no distance (:1018)
+  a.n = n;
+  a.skip = std::min(skip, n);   // (no rank reaches n: the window's end cannot overflow)
+  a.limit = std::min(limit, n);
+  a.id_base = id_base_;
+  a.id_stride = id_stride_;
+  const int64_t nblocks = select_blocks(n);
+  const size_t counts_bytes = ((size_t)nblocks * sizeof(u32) + 7) & ~(size_t)7;
+  if (!sel_bits_.reserve((size_t)nblocks * (SEL_ROWS / 8)) || !sel_scan_.reserve(counts_bytes + (size_t)(nblocks + 1) * sizeof(int64_t)) ||
+      (!out_dev && !sel_out_.reserve((size_t)(2 + a.limit) * sizeof(int64_t))))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "select: out of device memory (scratch)");
+  a.bits = sel_bits_.as<u64>();
+  a.counts = sel_scan_.as<u32>();
+  a.offsets = reinterpret_cast<int64_t*>(sel_scan_.as<char>() + counts_bytes);
+  a.ids_out = out_dev ? ids_out : sel_out_.as<int64_t>() + 2;
+  a.count_out = out_dev ? count_out : sel_out_.as<int64_t>();
+  a.total_out = out_dev ? total_out : sel_out_.as<int64_t>() + 1;
+  launch_select(a, stream_);
+  HIP_TRY(hipGetLastError());
+  if (!out_dev) {   // count and total first: only the ids of the window cross PCIe, not `limit` slots
+    int64_t head[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(head, sel_out_.p, sizeof(head), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (head[0] > 0) {
+      HIP_TRY(hipMemcpyAsync(ids_out, a.ids_out, (size_t)head[0] * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+      HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    *count_out = head[0];
+    if (total_out) *total_out = head[1];
+  }
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ search_range
+// Every visible row with exact fp32 distance <= radius[j]: the total, and the cap closest by (distance, id).  One pass finds the survivors - the
+// matrix form (one launch of the lower-bound filter + the exact tail, flat_range_lists) or the stream form (range_scan_kernel) - one launch orders
+// them (range.hip), one host sync reads every query's status and total (host outputs: a second one brings the results, once).  What is left to the host after it, both counted in overflow_queries:
+//   RANGE_RESCAN  the filter's candidate list was too short: the query runs again on the stream form;
+//   RANGE_TOPK    more survivors than cap: the cap closest come from flat_stream (k = cap), the total is already counted.
+// Reports like a search (statistics, kernel ring); changes nothing a later search can observe.
+int32_t Index::search_range(const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* pp, int64_t* ids, float* dist,
+                            int32_t* counts, int64_t* totals) {
+  eps_search_params p;
+  if (pp) p = *pp; else eps_default_search_params(&p);
+  if (nq < 0) return fail(EPS_USER_ERROR, "search_range: nq must be >= 0");
+  if (cap < 1 || cap > RANGE_MAX_CAP) return fail(EPS_USER_ERROR, "search_range: cap must be in [1, 8192]");
+  if (nq == 0) return EPS_OK;
+  if (!queries || !radius || !ids || !dist) return fail(EPS_USER_ERROR, "search_range: null buffer");
+  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_range: unknown flat engine");
+  HIP_TRY(hipSetDevice(device_));
+  if (is_device_ptr(radius)) return fail(EPS_USER_ERROR, "search_range: radius must be a host array");
+  for (int64_t j = 0; j < nq; ++j)
+    if (radius[j] != radius[j]) return fail(EPS_USER_ERROR, "search_range: a radius is NaN");
+  int32_t rc = check_filters_cover_table("search_range");
+  if (rc != EPS_OK) return rc;
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)) || (totals && out_dev != is_device_ptr(totals)))
+    return fail(EPS_USER_ERROR, "search_range: ids_out, dist_out, counts_out and totals_out must all be host or all be device pointers");
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
+  const int64_t n = n_rows_;
+
+  // ---- scratch.  Device: [counts | status | candidates re-ranked], [radii | fall-back query numbers]; page-locked: [radii | read-back | query numbers]
+  const size_t rb_bytes = (((size_t)nq * 8 + 7) & ~(size_t)7) + 8, rad_bytes = ((size_t)nq * 4 + 7) & ~(size_t)7;
+  const size_t ids_bytes = (size_t)nq * cap * sizeof(int64_t), tot_bytes = (size_t)nq * sizeof(int64_t), dist_bytes = (size_t)nq * cap * sizeof(float);
+  const size_t out_bytes = ids_bytes + tot_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
+  if (!rng_keys_.reserve((size_t)nq * cap * sizeof(u64)) || !rng_cnt_.reserve(rb_bytes) || !rng_in_.reserve(2 * rad_bytes) ||
+      (!out_dev && !rng_out_.reserve(out_bytes)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (scratch)");
+  if (!h_rng_.reserve(2 * rad_bytes + rb_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of page-locked host memory");
+  float* h_rad = static_cast<float*>(h_rng_.p);
+  u32* h_rb = reinterpret_cast<u32*>(static_cast<char*>(h_rng_.p) + rad_bytes);
+  int32_t* h_sel = reinterpret_cast<int32_t*>(static_cast<char*>(h_rng_.p) + rad_bytes + rb_bytes);
+  u32* d_cnt = rng_cnt_.as<u32>();
+  u32* d_status = d_cnt + nq;
+  unsigned long long* d_cand_total = reinterpret_cast<unsigned long long*>(rng_cnt_.as<char>() + rb_bytes - 8);
+  int32_t* d_sel = reinterpret_cast<int32_t*>(rng_in_.as<char>() + rad_bytes);
+
+  const float* dq;
+  rc = stage_queries("search_range", queries, nq, &dq);
+  if (rc != EPS_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(stream_));   // (the previous call's copies out of / into h_rng_ have completed)
+  memcpy(h_rad, radius, (size_t)nq * 4);
+  HIP_TRY(hipMemcpyAsync(rng_in_.p, h_rad, (size_t)nq * 4, hipMemcpyHostToDevice, stream_));
+  HIP_TRY(hipMemsetAsync(rng_cnt_.p, 0, rb_bytes, stream_));
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  const RangeLists L{rng_keys_.as<u64>(), d_cnt, rng_in_.as<float>(), cap};
+  const FilterSpec fs = filter_spec();
+  int64_t* d_ids = ids;
+  float* d_dist = dist;
+  int32_t* d_counts = counts;
+  int64_t* d_totals = totals;
+  if (!out_dev) {
+    d_ids = rng_out_.as<int64_t>();
+    d_totals = reinterpret_cast<int64_t*>(rng_out_.as<char>() + ids_bytes);
+    d_dist = reinterpret_cast<float*>(rng_out_.as<char>() + ids_bytes + tot_bytes);
+    d_counts = reinterpret_cast<int32_t*>(rng_out_.as<char>() + ids_bytes + tot_bytes + dist_bytes);
+  }
+  // the stream form over the `m` queries named by sel (null: all of them), in launches of at most 32768 queries (the grid's y extent)
+  auto scan = [&](const int32_t* sel, int64_t m) {
+    for (int64_t q0 = 0; q0 < m; q0 += 32768) {
+      RangeScanArgs a{d_rows_, n, (int)dim_, metric_, dq, std::min<int64_t>(32768, m - q0), sel ? sel + q0 : nullptr, fs, L};
+      if (!sel) {   // (query numbers count from the launch's first query)
+        a.queries = dq + q0 * dim_;
+        a.L = RangeLists{L.keys + q0 * cap, L.cnt + q0, L.radius + q0, cap};
+      }
+      launch_range_scan(a, stream_);
+    }
+    stats_.dist_evals += m * n;
+  };
+  auto order = [&](const int32_t* sel, int64_t m, const u64* topk) {
+    launch_range_order(RangeOrderArgs{m, sel, L, topk, d_status, id_base_, id_stride_, d_ids, d_dist, d_counts, d_totals}, stream_);
+  };
+  auto read_back = [&]() -> hipError_t {
+    const hipError_t er = hipMemcpyAsync(h_rb, rng_cnt_.p, rb_bytes, hipMemcpyDeviceToHost, stream_);   // (status and totals only: the results cross PCIe once, at the end)
+    return er == hipSuccess ? hipStreamSynchronize(stream_) : er;
+  };
+  auto pick = [&](u32 status, std::vector<int32_t>* sel) -> hipError_t {   // the queries left in `status`, their numbers on the device
+    sel->clear();
+    for (int64_t j = 0; j < nq; ++j)
+      if (h_rb[nq + j] == status) sel->push_back((int32_t)j);
+    if (sel->empty()) return hipSuccess;
+    memcpy(h_sel, sel->data(), sel->size() * 4);
+    return hipMemcpyAsync(d_sel, h_sel, sel->size() * 4, hipMemcpyHostToDevice, stream_);
+  };
+
+  // ---- the pass
+  int engine = p.flat_engine;
+  bool matrix = engine == EPS_FLAT_MFMA || engine == EPS_FLAT_MFMA_I8;
+  if (engine == EPS_FLAT_AUTO) {   // (the rule counts single-query calls towards building a mirror: that is a search's business)
+    const int64_t keep_version = small_calls_version_;
+    const int keep_calls = small_calls_;
+    matrix = flat_mfma_profitable(*this, nq, 1);
+    small_calls_version_ = keep_version;
+    small_calls_ = keep_calls;
+  }
+  bool served = false;
+  if (matrix) {
+    rc = flat_range_lists(*this, dq, nq, engine == EPS_FLAT_MFMA ? 16 : (engine == EPS_FLAT_MFMA_I8 ? 8 : 0), L, d_cand_total, &served);
+    if (rc != EPS_OK) return rc;
+  }
+  if (!served && n > 0) {
+    HIP_TRY(hipEventRecord(evk0_, stream_));
+    scan(nullptr, nq);
+    HIP_TRY(hipEventRecord(evk1_, stream_));
+    stats_.main_kernel_launches = 1;
+    stats_.main_kernel_rows = n;
+    stats_.main_kernel_queries = nq;
+    stats_.main_kernel_bits = 32;
+  }
+  order(nullptr, nq, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(read_back());
+  stats_.rerank_rows = (int64_t)*reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(h_rb) + rb_bytes - 8);
+
+  // ---- what the lists could not answer
+  const eps_search_stats pass_stats = stats_;
+  std::vector<int32_t> sel;
+  int64_t fell_back = 0;
+  HIP_TRY(pick(RANGE_RESCAN, &sel));
+  if (!sel.empty()) {
+    fell_back += (int64_t)sel.size();
+    launch_range_gather(dq, (int)dim_, d_sel, (int64_t)sel.size(), nullptr, d_cnt, true, stream_);
+    scan(d_sel, (int64_t)sel.size());
+    order(d_sel, (int64_t)sel.size(), nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(read_back());
+  }
+  std::vector<int32_t> rescanned;
+  rescanned.swap(sel);
+  HIP_TRY(pick(RANGE_TOPK, &sel));
+  if (!sel.empty()) {
+    const int64_t m = (int64_t)sel.size();
+    fell_back += m;
+    for (int32_t j : sel) fell_back -= std::binary_search(rescanned.begin(), rescanned.end(), j) ? 1 : 0;   // (a query counts once)
+    if (!tmp_buf_.reserve((size_t)m * dim_ * sizeof(float)) || !run_buf_.reserve((size_t)m * cap * sizeof(u64)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (fall-back)");
+    launch_range_gather(dq, (int)dim_, d_sel, m, tmp_buf_.as<float>(), d_cnt, false, stream_);
+    // (flat_stream times its scan with the call's main-kernel events: it gets a spare pair - no filter stage of this call uses one - so that
+    // main_kernel_ms stays the time of the pass, as the other main_kernel_* fields do)
+    hipEvent_t const k0 = evk0_, k1 = evk1_;
+    evk0_ = stage_ev_[STAGE_EV - 1][0];
+    evk1_ = stage_ev_[STAGE_EV - 1][1];
+    rc = flat_stream(tmp_buf_.as<float>(), m, cap, 0, n, run_buf_.as<u64>());
+    evk0_ = k0;
+    evk1_ = k1;
+    if (rc != EPS_OK) return rc;
+    order(d_sel, m, run_buf_.as<u64>());
+    HIP_TRY(hipGetLastError());
+  }
+  if (fell_back > 0) {   // the call's main kernel stays the pass
+    stats_.main_kernel_launches = pass_stats.main_kernel_launches;
+    stats_.main_kernel_rows = pass_stats.main_kernel_rows;
+    stats_.main_kernel_queries = pass_stats.main_kernel_queries;
+    stats_.main_kernel_bits = pass_stats.main_kernel_bits;
+  }
+  stats_.overflow_queries = fell_back;
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(rng_out_.p, out_bytes, {{ids, 0, ids_bytes}, {totals, ids_bytes, tot_bytes}, {dist, ids_bytes + tot_bytes, dist_bytes},
+                                               {counts, ids_bytes + tot_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    if (rc != EPS_OK) return rc;
+  }
+  end_timed_call();
+  return EPS_OK;
+}
+
+int32_t Index::last_stats(eps_search_stats* out) {
+  eps_search_stats s = stats_;
+  // event timings are read lazily: the caller may have left the work in flight
+  if (ev0_ && hipEventSynchronize(ev1_) == hipSuccess) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) s.kernel_ms = ms;
+    if (s.main_kernel_launches > 0 && hipEventElapsedTime(&ms, evk0_, evk1_) == hipSuccess) s.main_kernel_ms = ms;
+    double all = 0.0;
+    for (int i = 0; i < stage_n_; ++i)
+      if (hipEventElapsedTime(&ms, stage_ev_[i][0], stage_ev_[i][1]) == hipSuccess) all += ms;
+    s.filter_ms_all = all;
+  }
+  (void)hipGetLastError();
+  *out = s;
+  return EPS_OK;
+}
+
+// main-kernel milliseconds of the most recent search calls (oldest first); synchronises the stream
+int Index::kernel_times(double* ms_out, int cap) {
+  if (!ms_out || cap <= 0) return 0;
+  if (hipSetDevice(device_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  int n = 0;
+  const int64_t first = std::max<int64_t>(1, kring_seq_ - std::min<int64_t>(cap, KRING) + 1);
+  for (int64_t q = first; q <= kring_seq_; ++q) {
+    const int slot = (int)(q % KRING);
+    if (!kring_valid_[slot]) continue;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, kring_[slot][0], kring_[slot][1]) == hipSuccess) ms_out[n++] = ms;
+    else (void)hipGetLastError();
+  }
+  return n;
+}
+
+}  // namespace eps

@@ -617,17 +617,17 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   HalfMirror& m = *ix.mirror_;
   const int64_t n = ix.scan_limit_ >= 0 ? std::min(ix.scan_limit_, ix.n_rows_) : ix.n_rows_;
   // values beyond the fp16 range: the filter bound would be vacuous; the exact stream engine takes over
-  if (!i8 && !m.fp16_range_ok) return ix.flat_stream(dq, nq, k, 0, n, run_keys, false, -1, !approx);
+  if (!i8 && !m.fp16_range_ok) return ix.flat_stream(dq, nq, k, 0, n, run_keys, -1, !approx);
   auto fall_back = [&](Fallback to) -> int32_t {
     if (to == Fallback::fp16) return flat_mfma_search_slice(ix, dq, nq, k, run_keys, approx, 1, 16, false);
     if (to == Fallback::wide_lists) return flat_mfma_search_slice(ix, dq, nq, k, run_keys, approx, 16, 16, false);
-    return ix.flat_stream(dq, nq, k, 0, n, run_keys, false);
+    return ix.flat_stream(dq, nq, k, 0, n, run_keys);
   };
   hipStream_t s = ix.stream_;
   Chain c;
   rc = plan_chain(ix, m, dq, nq, k, run_keys, approx, cap_scale, i8, n, &c);
   if (rc == EPS_OK) rc = prepare_queries(ix, m, c);
-  if (rc == EPS_OK && !c.seeded) rc = ix.flat_stream(dq, nq, k, 0, c.bounds[0], run_keys, false, -1, !approx);   // stage 0: exact scan of the head
+  if (rc == EPS_OK && !c.seeded) rc = ix.flat_stream(dq, nq, k, 0, c.bounds[0], run_keys, -1, !approx);   // stage 0: exact scan of the head
   if (rc != EPS_OK) return rc;
   ix.stats_.main_kernel_launches = 0;
   m.s8_clean_cnt = nullptr;   // (the chain's counters live where the one-pass form keeps its own)
@@ -657,7 +657,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
   }
   er = hipGetLastError();
   if (er != hipSuccess) return ix.hip_fail(er, "MFMA filter launch");
-  if (!fin_done && ix.pre_sync_ && !approx && nq == ix.pre_sync_nq_) ix.pre_sync_();   // (speculative: a fall-back pass below converts again)
+  if (!fin_done && ix.call_.pre_sync && !approx && nq == ix.call_.nq) ix.call_.pre_sync();   // (speculative: a fall-back pass below converts again)
   er = read_counters(c.c, s, &h);
   if (er != hipSuccess) return ix.hip_fail(er, "MFMA filter");
   ix.stats_.rerank_rows += (int64_t)h.total;
@@ -675,7 +675,7 @@ int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u6
 // each XCD's 4 MB L2 while the row operand streams past; at 4096 / 8192 queries per pass the query fragments thrash L2
 // and the filter drops to 0.37 / 0.27 of the MFMA peak (0.46 in slices; bench.py --rows 1250000 --batch 8192).
 int32_t flat_mfma_search(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool approx, int bits) {
-  if (ix.n_rows_ <= 0) return ix.flat_stream(dq, nq, k, 0, 0, run_keys, false);   // (nothing to mirror)
+  if (ix.n_rows_ <= 0) return ix.flat_stream(dq, nq, k, 0, 0, run_keys);   // (nothing to mirror)
   const bool auto_bits = bits != 8 && bits != 16;
   if (auto_bits) bits = 8;   // the library's choice: 8-bit first pass - tables it cannot serve fall back by themselves
   const int64_t slice = std::max(256, tune_int("EPS_MFMA_MAX_BATCH", 2048));

@@ -148,10 +148,10 @@ inline RerankArgs rerank_args(const Index& ix, const HalfMirror& m, const float*
 }
 // the call's LAST re-rank writes the caller-visible result itself where search() asked for that: true = this launch does
 inline bool finalize_in_rerank(const Index& ix, int64_t nq, RerankArgs* ra) {
-  if (!(ix.pre_sync_ && nq == ix.pre_sync_nq_ && ix.fin_ids_ != nullptr)) return false;
-  ra->fin_ids = ix.fin_ids_;
-  ra->fin_dist = ix.fin_dist_;
-  ra->fin_counts = ix.fin_cnt_;
+  if (!(ix.call_.pre_sync && nq == ix.call_.nq && ix.call_.fin_ids != nullptr)) return false;
+  ra->fin_ids = ix.call_.fin_ids;
+  ra->fin_dist = ix.call_.fin_dist;
+  ra->fin_counts = ix.call_.fin_cnt;
   ra->fin_base = ix.id_base_;
   ra->fin_stride = ix.id_stride_;
   return true;

@@ -249,7 +249,7 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
   if (fin_here) (void)hipEventRecord(ix.ev1_, s);
   hipError_t er = hipGetLastError();
   if (er != hipSuccess) return ix.hip_fail(er, "one-pass flat search launch");
-  if (!fin_here && ix.pre_sync_ && nq == ix.pre_sync_nq_) ix.pre_sync_();
+  if (!fin_here && ix.call_.pre_sync && nq == ix.call_.nq) ix.call_.pre_sync();
   CountersRead h;
   er = read_counters(m, c, host_words, s, &h);
   if (er != hipSuccess) return ix.hip_fail(er, "one-pass flat search");

@@ -471,7 +471,7 @@ int32_t graph_search_impl(Index& ix, const float* dq, int64_t nq, int k, const e
   const int tail_k = std::min(limit, 8192);            // only min(|tail|, limit) tail entries are ever merged (:890-899)
   if (n_total > n) {
     if (!g.tail.reserve((size_t)nq * tail_k * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory");
-    int32_t rc = ix.flat_stream(dq, nq, tail_k, n, n_total, g.tail.as<u64>(), false);
+    int32_t rc = ix.flat_stream(dq, nq, tail_k, n, n_total, g.tail.as<u64>());
     if (rc != EPS_OK) return rc;
     tail = g.tail.as<u64>();
   }
