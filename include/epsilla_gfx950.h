@@ -28,6 +28,10 @@
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
+ *   eps_merge_range / _packed       (new) joins the answers G shards gave to one eps_index_search_range into the unsharded table's answer
+ *   eps_merge_select                (new) the same for eps_index_select: a window over the shards' ordered ids, and the totals added up
+ *   eps_exchange_allgather_merge_range  (new) the exchange step of a sharded radius search: one all-gather, one merge launch
+ *                                   The reference has no counterpart of these: it does not shard a table
  *
  * Pointer arguments documented "host or device" are classified with hipPointerGetAttributes; device
  * pointers are used in place (no copy) on the index's stream.  Every function returns a status code
@@ -418,6 +422,35 @@ int32_t eps_merge_topk(const float* dist, const int64_t* ids, int32_t shards, in
 int32_t eps_merge_topk_packed(const void* gathered, int64_t shard_stride_bytes, int64_t dist_offset_bytes, int32_t shards,
                               int64_t nq, int32_t k, float* out_dist, int64_t* out_ids, int32_t device, void* hip_stream);
 
+/* ---- Radius search and ordered select across shards.  The reference has no counterpart (it does not shard a table): G single-device
+ * indices, shard s holding the rows i with i mod G = s and eps_index_set_id_map(base = s, stride = G), each answer the whole call over their rows;
+ * these calls join the G answers into exactly the answer of ONE index over the whole table.  One launch (csrc/merge_lists.hip): every list element
+ * finds its own output slot - its position plus, from one binary search per other list, the number of keys before it (`<=` against the shards before
+ * it, `<` against those after: equal keys are ordered by shard number) - no serial merge, no sort.
+ *
+ * eps_merge_range: ids / dist [shards][nq][cap], counts int32 [shards][nq], totals int64 [shards][nq] = what eps_index_search_range wrote on every
+ * shard (global ids through each shard's id map).  A list's valid length is its counts entry; keys order as everywhere in the library, by (distance,
+ * id), -0 = +0, every NaN after +inf.  out_totals[j] = the sum of totals[s][j]; out_counts[j] = min(that, cap); out_ids[j] / out_dist[j] = the count
+ * smallest keys in ascending order, the unused slots -1 / +inf: the contract of eps_index_search_range - also where a shard's own total exceeded cap,
+ * since the cap closest of the union lie among the per-shard cap closest.  out_counts and out_totals may be NULL.  1 <= cap <= 8192,
+ * 1 <= shards <= 16 (else EPS_USER_ERROR), nq = 0: EPS_OK.  Lists and results are all host or all device buffers (a mixed set: EPS_USER_ERROR):
+ * host buffers are staged and the call synchronises; device buffers are used in place, asynchronously on hip_stream.
+ * eps_range_pack_bytes: the size of ONE shard's packed answer, ids i64[nq][cap] | totals i64[nq] | dist f32[nq][cap] | counts i32[nq], rounded up to
+ * a multiple of 8 (-1: nq or cap out of range).  eps_merge_range_packed: the same merge over one gathered DEVICE buffer in which shard s's packed
+ * answer starts at s * shard_stride_bytes (a multiple of 8, >= eps_range_pack_bytes) - what one all-gather of packed answers delivers.
+ *
+ * eps_merge_select: ids [shards][len], counts [shards], totals [shards] = what eps_index_select(skip = 0, limit = len) wrote on every shard.
+ * out_ids[0 .. count) = ranks [skip, skip + limit) of the ascending merged ids, *count_out = clamp(sum of counts - skip, 0, limit), *total_out (may be
+ * NULL) = the sum of totals.  A shard's list must reach as far as the window can: len < skip + limit is EPS_USER_ERROR, and so is a negative len,
+ * skip or limit; limit = 0: count 0.  Host or device as above. */
+int32_t eps_merge_range(const int64_t* ids, const float* dist, const int32_t* counts, const int64_t* totals, int32_t shards, int64_t nq, int32_t cap,
+                        int64_t* out_ids, float* out_dist, int32_t* out_counts, int64_t* out_totals, int32_t device, void* hip_stream);
+int64_t eps_range_pack_bytes(int64_t nq, int32_t cap);
+int32_t eps_merge_range_packed(const void* gathered, int64_t shard_stride_bytes, int32_t shards, int64_t nq, int32_t cap, int64_t* out_ids, float* out_dist,
+                               int32_t* out_counts, int64_t* out_totals, int32_t device, void* hip_stream);
+int32_t eps_merge_select(const int64_t* ids, const int64_t* counts, const int64_t* totals, int32_t shards, int64_t len, int64_t skip, int64_t limit,
+                         int64_t* out_ids, int64_t* count_out, int64_t* total_out, int32_t device, void* hip_stream);
+
 /* ---- The exchange step of the sharded path, owned by the library (r6).  One process per GPU: every rank holds, for the whole
  * batch, the top-k lists over ITS shard (global ids); eps_exchange_allgather_merge packs them as [ids int64[nq][k] | dist f32[nq][k]]
  * (12 k nq bytes per rank), runs ONE ncclAllGather on the RCCL communicator the handle owns (xGMI inside a node) and merges the `world`
@@ -433,6 +466,12 @@ int32_t eps_exchange_unique_id(void* id128);
 int32_t eps_exchange_create(int32_t rank, int32_t world, const void* id128, int32_t device, eps_exchange** out);
 int32_t eps_exchange_allgather_merge(eps_exchange* x, const int64_t* ids, const float* dist, int64_t nq, int32_t k, int64_t* out_ids, float* out_dist,
                                      void* hip_stream);
+/* The same step for a radius search: every rank holds its shard's answer of eps_index_search_range for the whole batch; the call packs it into the
+ * rank's slot of the gathered buffer (eps_range_pack_bytes per rank), runs ONE ncclAllGather and the launch of eps_merge_range_packed - every rank
+ * ends with the unsharded answer.  Device buffers only; out_counts / out_totals may be NULL; eps_exchange_times reports the call like a top-k
+ * exchange.  The mailbox form does not serve it. */
+int32_t eps_exchange_allgather_merge_range(eps_exchange* x, const int64_t* ids, const float* dist, const int32_t* counts, const int64_t* totals, int64_t nq,
+                                           int32_t cap, int64_t* out_ids, float* out_dist, int32_t* out_counts, int64_t* out_totals, void* hip_stream);
 /* device time of the two parts - all-gather, merge - of the last calls (hipEvents on their stream, kept for 64 calls; waits for them):
  * us_pairs[2 i], us_pairs[2 i + 1] for the oldest .. newest of min(calls, 64, max_calls) calls; returns how many (-1: failure) */
 int32_t eps_exchange_times(eps_exchange* x, double* us_pairs, int32_t max_calls);

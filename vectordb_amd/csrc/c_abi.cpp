@@ -47,6 +47,30 @@ static int32_t on_single_device(eps_index* h, const char* refusal, int32_t err_c
   }
 }
 
+// The merges have no handle to keep a message in: a refusal names its reason on stderr, as a failed eps_index_create does.
+static int32_t merge_refused(const char* entry, const char* why, int32_t rc) {
+  std::fprintf(stderr, "%s: %s\n", entry, why);
+  return rc;
+}
+// what merge_host.hpp's staging runs on: the current device, one stream
+struct HipMergeDev {
+  hipStream_t s;
+  bool is_device(const void* p) { return eps::is_device_ptr(p); }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    return p;
+  }
+  void free(void* p) { (void)hipFree(p); }
+  bool h2d(void* dst, const void* src, size_t bytes) { return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess; }
+  bool d2h(void* dst, const void* src, size_t bytes) { return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) == hipSuccess; }
+  void launch(const eps::MergeRankArgs& a) { eps::launch_merge_rank(a, s); }
+  bool sync() { return hipStreamSynchronize(s) == hipSuccess && hipGetLastError() == hipSuccess; }
+};
+
 extern "C" {
 
 void eps_default_search_params(eps_search_params* p) {
@@ -282,6 +306,62 @@ int32_t eps_merge_topk_packed(const void* gathered, int64_t shard_stride_bytes, 
   const char* base = static_cast<const char*>(gathered);
   eps::launch_merge_shards(reinterpret_cast<const float*>(base + dist_offset_bytes), reinterpret_cast<const int64_t*>(base), shards, nq, k,
                            out_dist, out_ids, static_cast<hipStream_t>(stream), shard_stride_bytes);
+  return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+// ---- the merges of radius answers and ordered selects (merge_lists.hip; checks and host staging: merge_host.hpp)
+int32_t eps_merge_range(const int64_t* ids, const float* dist, const int32_t* counts, const int64_t* totals, int32_t shards, int64_t nq, int32_t cap,
+                        int64_t* out_ids, float* out_dist, int32_t* out_counts, int64_t* out_totals, int32_t device, void* stream) {
+  const char* why;
+  const int32_t rc = eps::merge_range_check(shards, nq, cap, &why);
+  if (rc != EPS_OK) return merge_refused("eps_merge_range", why, rc);
+  if (nq == 0) return EPS_OK;
+  if (!ids || !dist || !counts || !totals || !out_ids || !out_dist) return merge_refused("eps_merge_range", "null pointer", EPS_USER_ERROR);
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  HipMergeDev dev{static_cast<hipStream_t>(stream)};
+  const void* ptrs[] = {ids, dist, counts, totals, out_ids, out_dist, out_counts, out_totals};
+  const int side = eps::merge_side(dev, ptrs, 8);
+  if (side < 0) return merge_refused("eps_merge_range", "lists and results must all be host or all be device buffers", EPS_USER_ERROR);
+  if (side == 0) return eps::merge_range_host(dev, ids, dist, counts, totals, shards, nq, cap, out_ids, out_dist, out_counts, out_totals);
+  const int64_t nk = nq * cap;
+  dev.launch(eps::merge_range_args(ids, nk * 8, dist, nk * 4, counts, nq * 4, totals, nq * 8, shards, nq, cap, out_ids, out_dist, out_counts, out_totals));
+  return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+int64_t eps_range_pack_bytes(int64_t nq, int32_t cap) {
+  if (nq < 0 || cap < 1 || cap > eps::MERGE_MAX_CAP || !eps::merge_sizes_ok(1, nq, cap)) return -1;
+  return eps::range_pack(nq, cap).bytes;
+}
+
+int32_t eps_merge_range_packed(const void* gathered, int64_t shard_stride_bytes, int32_t shards, int64_t nq, int32_t cap, int64_t* out_ids, float* out_dist,
+                               int32_t* out_counts, int64_t* out_totals, int32_t device, void* stream) {
+  const char* why;
+  const int32_t rc = eps::merge_range_check(shards, nq, cap, &why);
+  if (rc != EPS_OK) return merge_refused("eps_merge_range_packed", why, rc);
+  if (shard_stride_bytes < eps::range_pack(nq, cap).bytes || (shard_stride_bytes & 7))
+    return merge_refused("eps_merge_range_packed", "shard_stride_bytes must be a multiple of 8 and at least eps_range_pack_bytes", EPS_USER_ERROR);
+  if (nq == 0) return EPS_OK;
+  if (!gathered || !out_ids || !out_dist) return merge_refused("eps_merge_range_packed", "null pointer", EPS_USER_ERROR);
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  HipMergeDev dev{static_cast<hipStream_t>(stream)};
+  const void* ptrs[] = {gathered, out_ids, out_dist, out_counts, out_totals};
+  if (eps::merge_side(dev, ptrs, 5) != 1) return merge_refused("eps_merge_range_packed", "the gathered buffer and the results are device buffers", EPS_USER_ERROR);
+  dev.launch(eps::merge_range_args_packed(gathered, shard_stride_bytes, shards, nq, cap, out_ids, out_dist, out_counts, out_totals));
+  return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+int32_t eps_merge_select(const int64_t* ids, const int64_t* counts, const int64_t* totals, int32_t shards, int64_t len, int64_t skip, int64_t limit,
+                         int64_t* out_ids, int64_t* count_out, int64_t* total_out, int32_t device, void* stream) {
+  const char* why;
+  const int32_t rc = eps::merge_select_check((ids || len == 0) && counts && totals && (out_ids || limit == 0) && count_out, shards, len, skip, limit, &why);
+  if (rc != EPS_OK) return merge_refused("eps_merge_select", why, rc);
+  if (hipSetDevice(device) != hipSuccess) return EPS_INFRA_UNEXPECTED_ERROR;
+  HipMergeDev dev{static_cast<hipStream_t>(stream)};
+  const void* ptrs[] = {len ? ids : nullptr, counts, totals, limit ? out_ids : nullptr, count_out, total_out};
+  const int side = eps::merge_side(dev, ptrs, 6);
+  if (side < 0) return merge_refused("eps_merge_select", "lists and results must all be host or all be device buffers", EPS_USER_ERROR);
+  if (side == 0) return eps::merge_select_host(dev, ids, counts, totals, shards, len, skip, limit, out_ids, count_out, total_out);
+  dev.launch(eps::merge_select_args(ids, counts, totals, shards, len, skip, limit, out_ids, count_out, total_out));
   return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
 }
 

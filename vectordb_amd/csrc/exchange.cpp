@@ -210,6 +210,43 @@ int32_t eps_exchange_allgather_merge(eps_exchange* x, const int64_t* ids, const 
   return hipGetLastError() == hipSuccess ? EPS_OK : x->fail(EPS_INFRA_UNEXPECTED_ERROR, "eps_exchange: merge launch");
 }
 
+// The same step for a radius search: every rank holds the answer of eps_index_search_range over ITS shard (global ids); the four arrays are packed
+// into the rank's slot of the gathered buffer in the layout of eps_range_pack_bytes, ONE ncclAllGather, merge_rank_kernel (merge_lists.hip).
+int32_t eps_exchange_allgather_merge_range(eps_exchange* x, const int64_t* ids, const float* dist, const int32_t* counts, const int64_t* totals, int64_t nq,
+                                           int32_t cap, int64_t* out_ids, float* out_dist, int32_t* out_counts, int64_t* out_totals, void* hip_stream) {
+  if (!x) return EPS_USER_ERROR;
+  if (!x->comm) return x->fail(EPS_USER_ERROR, "eps_exchange: no communicator (create failed)");
+  const char* why;
+  const int32_t rc = eps::merge_range_check(x->world, nq, cap, &why);
+  if (rc != EPS_OK) return x->fail(rc, std::string("eps_exchange_allgather_merge_range: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (!ids || !dist || !counts || !totals || !out_ids || !out_dist) return x->fail(EPS_USER_ERROR, "eps_exchange_allgather_merge_range: null pointer");
+  for (const void* p : {(const void*)ids, (const void*)dist, (const void*)counts, (const void*)totals, (const void*)out_ids, (const void*)out_dist,
+                        (const void*)out_counts, (const void*)out_totals})
+    if (p && !eps::is_device_ptr(p)) return x->fail(EPS_USER_ERROR, "eps_exchange_allgather_merge_range: lists and results live on the rank's device");
+  if (hipSetDevice(x->device) != hipSuccess) return x->fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  Rccl& r = rccl();
+  const eps::RangePack pk = eps::range_pack(nq, cap);
+  const size_t stride = (size_t)pk.bytes, nk = (size_t)nq * (size_t)cap;
+  if (!x->gathered.reserve(stride * (size_t)x->world)) return x->fail(EPS_INFRA_UNEXPECTED_ERROR, "eps_exchange: out of device memory");
+  char* mine = static_cast<char*>(x->gathered.p) + stride * (size_t)x->rank;   // the all-gather runs in place
+  if (hipMemcpyAsync(mine, ids, nk * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(mine + pk.totals_off, totals, (size_t)nq * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(mine + pk.dist_off, dist, nk * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(mine + pk.counts_off, counts, (size_t)nq * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return x->fail(EPS_INFRA_UNEXPECTED_ERROR, "eps_exchange: pack copy");
+  hipEvent_t* ev = x->ev[x->calls % eps_exchange::RING];
+  (void)hipEventRecord(ev[0], s);
+  const ncclResult_t nrc = r.AllGather(mine, x->gathered.p, stride, ncclUint8, x->comm, s);
+  if (nrc != ncclSuccess) return x->fail(EPS_INFRA_UNEXPECTED_ERROR, std::string("ncclAllGather: ") + r.GetErrorString(nrc));
+  (void)hipEventRecord(ev[1], s);
+  eps::launch_merge_rank(eps::merge_range_args_packed(x->gathered.p, (int64_t)stride, x->world, nq, cap, out_ids, out_dist, out_counts, out_totals), s);
+  (void)hipEventRecord(ev[2], s);
+  x->calls += 1;
+  return hipGetLastError() == hipSuccess ? EPS_OK : x->fail(EPS_INFRA_UNEXPECTED_ERROR, "eps_exchange: merge launch");
+}
+
 static int32_t mbox_alloc(eps_exchange* x) {
   if (x->mbox) return EPS_OK;
   if (hipSetDevice(x->device) != hipSuccess) return x->fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");

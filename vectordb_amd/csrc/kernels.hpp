@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "device_common.hpp"
+#include "merge_host.hpp"
 
 namespace eps {
 
@@ -166,5 +167,9 @@ struct RangeOrderArgs {
 void launch_range_order(const RangeOrderArgs& a, hipStream_t s);
 // the queries named by qsel, copied next to each other (out, may be null); zero_cnt: their survivor counts start again at 0
 void launch_range_gather(const float* queries, int dim, const int32_t* qsel, int64_t m, float* out, u32* cnt, bool zero_cnt, hipStream_t s);
+
+// ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
+// a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch
+void launch_merge_rank(const MergeRankArgs& a, hipStream_t s);
 
 }  // namespace eps

@@ -578,6 +578,21 @@ class Exchange:
             raise EpsillaError(rc, self.L.eps_exchange_last_error(self.h).decode())
         return out_ids, out_dist
 
+    def allgather_merge_range(self, ids, dist, counts, totals, out=None, stream=None):
+        """this rank's answer of GpuIndex.search_range over its shard (device tensors: ids int64 / dist float32 [nq, cap], counts int32 [nq], totals
+        int64 [nq]) -> (ids, dist, counts, totals) of the unsharded table, on every rank; out=: caller-provided device tensors of those shapes"""
+        nq, cap = (int(v) for v in ids.shape)
+        _check_range_out(ids, dist, counts, totals, nq, cap)
+        if out is None:
+            import torch
+            out = (torch.empty_like(ids), torch.empty_like(dist), torch.empty_like(counts), torch.empty_like(totals))
+        _check_range_out(*out, nq, cap)
+        rc = self.L.eps_exchange_allgather_merge_range(self.h, _ptr(ids), _ptr(dist), _ptr(counts), _ptr(totals), nq, cap, _ptr(out[0]), _ptr(out[1]),
+                                                       _ptr(out[2]), _ptr(out[3]), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise EpsillaError(rc, self.L.eps_exchange_last_error(self.h).decode())
+        return tuple(out)
+
     def times_us(self, max_calls=64):
         """[(all-gather us, merge us)] of the last calls, oldest first (waits for them)"""
         buf = (C.c_double * (2 * max_calls))()
@@ -617,6 +632,175 @@ def merge_topk(dist, ids, out_dist, out_ids, device=0, stream=None):
     if rc != 0:
         raise EpsillaError(rc, "eps_merge_topk failed")
     return out_dist, out_ids
+
+
+# ---- radius search and ordered select across shards (eps_merge_range, eps_merge_range_packed, eps_merge_select; csrc/merge_lists.hip)
+MERGE_MAX_SHARDS, MERGE_MAX_CAP = 16, 8192
+
+
+def _empty_like_kind(like, shape, dtype):
+    """a result buffer of the kind `like` is: a NumPy array, or a tensor on like's device"""
+    if _is_dev(like):
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+    return np.empty(shape, dtype)
+
+
+def _check_lists(what, bufs):
+    """bufs: (array, name, shape, dtype) - all NumPy or all device, C-contiguous, of that dtype and shape; or a ValueError before the C ABI reads them"""
+    if len({_is_dev(a) for a, _, _, _ in bufs}) != 1:
+        raise ValueError("%s: %s must all be NumPy arrays or all be device tensors" % (what, ", ".join(name for _, name, _, _ in bufs)))
+    for a, name, shape, dtype in bufs:
+        got_dtype = str(a.dtype).replace("torch.", "")
+        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
+        if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
+            raise ValueError("%s: %s must be a C-contiguous %s array of shape %s, got %s %s%s"
+                             % (what, name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+
+
+def _merge_refusal(shards, cap=1, nq=0, length=0, skip=0, limit=0):
+    """why the library refused a merge (it has no handle to leave a message in)"""
+    why = []
+    if not 1 <= shards <= MERGE_MAX_SHARDS:
+        why.append("shards = %d, must be in 1 .. %d" % (shards, MERGE_MAX_SHARDS))
+    if not 1 <= cap <= MERGE_MAX_CAP:
+        why.append("cap = %d, must be in 1 .. %d" % (cap, MERGE_MAX_CAP))
+    if nq < 0 or length < 0 or skip < 0 or limit < 0:
+        why.append("negative nq, len, skip or limit")
+    elif length < skip + limit:
+        why.append("len = %d < skip + limit = %d: a shard's list must reach as far as the window" % (length, skip + limit))
+    return "; ".join(why) or "refused (a null or mixed host / device buffer?)"
+
+
+def range_pack_bytes(nq, cap):
+    """eps_range_pack_bytes: one shard's packed radius answer, ids i64[nq][cap] | totals i64[nq] | dist f32[nq][cap] | counts i32[nq], rounded up to 8"""
+    return int(lib.load().eps_range_pack_bytes(nq, cap))
+
+
+def merge_range(ids, dist, counts, totals, out=None, device=0, stream=None):
+    """eps_merge_range: ids int64 / dist float32 [shards, nq, cap], counts int32 [shards, nq], totals int64 [shards, nq] - every shard's answer of
+    search_range to the same queries, global ids - all NumPy or all device tensors.  Returns (ids [nq, cap], dist [nq, cap], counts [nq], totals [nq])
+    of the unsharded table, of the same kind (out=: caller-provided buffers of that kind).  Device tensors: asynchronous on `stream`."""
+    L = lib.load()
+    if len(ids.shape) != 3:
+        raise ValueError("merge_range: ids must have shape [shards, nq, cap], got %s" % (tuple(ids.shape),))
+    shards, nq, cap = (int(v) for v in ids.shape)
+    _check_lists("merge_range", ((ids, "ids", (shards, nq, cap), "int64"), (dist, "dist", (shards, nq, cap), "float32"),
+                                 (counts, "counts", (shards, nq), "int32"), (totals, "totals", (shards, nq), "int64")))
+    if out is None:
+        out = (_empty_like_kind(ids, (nq, cap), "int64"), _empty_like_kind(ids, (nq, cap), "float32"), _empty_like_kind(ids, (nq,), "int32"),
+               _empty_like_kind(ids, (nq,), "int64"))
+    _check_range_out(*out, nq, cap)
+    if _is_dev(out[0]) != _is_dev(ids):
+        raise ValueError("merge_range: lists and out= must all be NumPy arrays or all be device tensors")
+    rc = L.eps_merge_range(_ptr(ids), _ptr(dist), _ptr(counts), _ptr(totals), shards, nq, cap, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                           device, C.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise EpsillaError(rc, "eps_merge_range: " + _merge_refusal(shards, cap, nq))
+    return tuple(out)
+
+
+def merge_range_packed(gathered, shard_stride_bytes, shards, nq, cap, out=None, device=0, stream=None):
+    """eps_merge_range_packed: gathered = one device buffer in which shard s's packed answer (range_pack_bytes) starts at s * shard_stride_bytes"""
+    L = lib.load()
+    shards, nq, cap = int(shards), int(nq), int(cap)
+    if not _is_dev(gathered):
+        raise ValueError("merge_range_packed: gathered must be a device tensor")
+    if 1 <= shards <= MERGE_MAX_SHARDS and gathered.numel() * gathered.element_size() < shards * int(shard_stride_bytes):
+        raise ValueError("merge_range_packed: gathered holds %d bytes, %d shards of %d bytes are needed"
+                         % (gathered.numel() * gathered.element_size(), shards, shard_stride_bytes))
+    if out is None:
+        out = (_empty_like_kind(gathered, (nq, max(cap, 0)), "int64"), _empty_like_kind(gathered, (nq, max(cap, 0)), "float32"),
+               _empty_like_kind(gathered, (nq,), "int32"), _empty_like_kind(gathered, (nq,), "int64"))
+    _check_range_out(*out, nq, cap)
+    rc = L.eps_merge_range_packed(_ptr(gathered), int(shard_stride_bytes), shards, nq, cap, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                  device, C.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise EpsillaError(rc, "eps_merge_range_packed: " + (_merge_refusal(shards, cap, nq) if not (1 <= shards <= MERGE_MAX_SHARDS and 1 <= cap <= MERGE_MAX_CAP)
+                                                             else "shard_stride_bytes must be a multiple of 8 and at least range_pack_bytes; device buffers only"))
+    return tuple(out)
+
+
+def merge_select(ids, counts, totals, skip=0, limit=None, out=None, device=0, stream=None):
+    """eps_merge_select: ids int64 [shards, len], counts int64 [shards], totals int64 [shards] - every shard's answer of select(0, len), global ids -
+    all NumPy or all device tensors.  Ranks [skip, skip + limit) of the merged ascending ids (limit=None: len - skip) and the total, as
+    GpuIndex.select returns them: NumPy -> (ids of the window, total); device -> (ids [limit], counts [2] = count, total), asynchronous on `stream`.
+    out=(ids int64 [limit], counts int64 [2]) of the lists' kind."""
+    L = lib.load()
+    if len(ids.shape) != 2:
+        raise ValueError("merge_select: ids must have shape [shards, len], got %s" % (tuple(ids.shape),))
+    shards, length = (int(v) for v in ids.shape)
+    skip = int(skip)
+    limit = max(length - skip, 0) if limit is None else int(limit)
+    _check_lists("merge_select", ((ids, "ids", (shards, length), "int64"), (counts, "counts", (shards,), "int64"), (totals, "totals", (shards,), "int64")))
+    if out is None:
+        out = (_empty_like_kind(ids, (max(limit, 0),), "int64"), _empty_like_kind(ids, (2,), "int64"))
+    out_ids, out_counts = out
+    _check_select_out(out_ids, out_counts, max(limit, 0))
+    if _is_dev(out_ids) != _is_dev(ids):
+        raise ValueError("merge_select: lists and out= must all be NumPy arrays or all be device tensors")
+    total_ptr = C.c_void_p(_ptr(out_counts).value + 8)
+    rc = L.eps_merge_select(_ptr(ids), _ptr(counts), _ptr(totals), shards, length, skip, limit, _ptr(out_ids), _ptr(out_counts), total_ptr, device,
+                            C.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise EpsillaError(rc, "eps_merge_select: " + _merge_refusal(shards, 1, 0, length, skip, limit))
+    if _is_dev(out_counts):
+        return out_ids, out_counts
+    return out_ids[:int(out_counts[0])], int(out_counts[1])
+
+
+def _check_shards(what, shards):
+    shards = list(shards)
+    if not 1 <= len(shards) <= MERGE_MAX_SHARDS:
+        raise EpsillaError(lib.EPS_USER_ERROR, "%s: %d shards, must be 1 .. %d" % (what, len(shards), MERGE_MAX_SHARDS))
+    return shards
+
+
+def search_range_shards(shards, queries, radius, cap, flat_engine="auto"):
+    """GpuIndex.search_range of a table held by G single-device indices, shard s holding the rows i with i mod G = s and set_id_map(s, G): every
+    shard answers the whole batch over its rows, merge_range joins the answers.  Returns what GpuIndex.search_range returns for the whole table, bit
+    for bit: NumPy queries give NumPy arrays; device queries give tensors on the queries' device (the shards' calls are waited for, the merge is
+    asynchronous on the null stream: synchronise the device before reading)."""
+    shards = _check_shards("search_range_shards", shards)
+    G, cap = len(shards), int(cap)
+    dev = _is_dev(queries)
+    if not dev:
+        queries = np.ascontiguousarray(queries, np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+    nq = int(queries.shape[0])
+    c = max(cap, 0)
+    ids = _empty_like_kind(queries, (G, nq, c), "int64")
+    dist = _empty_like_kind(queries, (G, nq, c), "float32")
+    counts = _empty_like_kind(queries, (G, nq), "int32")
+    totals = _empty_like_kind(queries, (G, nq), "int64")
+    for s, ix in enumerate(shards):
+        ix.search_range(queries, radius, cap, flat_engine=flat_engine, out=(ids[s], dist[s], counts[s], totals[s]))
+    if dev:
+        for ix in shards:
+            ix.synchronize()
+    return merge_range(ids, dist, counts, totals, device=shards[0].device)
+
+
+def select_shards(shards, skip=0, limit=None):
+    """GpuIndex.select of a table held by G single-device indices (as search_range_shards): every shard lists its first skip + limit visible rows,
+    merge_select cuts the window out of their merged order.  Returns (ids of the window, total) as GpuIndex.select does; limit=None: all rows."""
+    shards = _check_shards("select_shards", shards)
+    G = len(shards)
+    rows = int(sum(ix.row_count for ix in shards))
+    skip = int(skip)
+    limit = rows if limit is None else int(limit)
+    if skip < 0 or limit < 0:
+        raise EpsillaError(lib.EPS_USER_ERROR, "select_shards: negative skip or limit")
+    skip = min(skip, rows)               # (no rank reaches the number of rows: the window is cut to what can exist,
+    window = min(limit, rows - skip)     #  and a shard's list reaches as far as it: skip + window ids at the most)
+    length = skip + window
+    ids = np.empty((G, length), np.int64)
+    counts = np.zeros((G, 2), np.int64)
+    for s, ix in enumerate(shards):
+        ix.select(0, length, out=(ids[s], counts[s]))
+    got, total = merge_select(ids, np.ascontiguousarray(counts[:, 0]), np.ascontiguousarray(counts[:, 1]), skip, window, device=shards[0].device)
+    return got, total
 
 
 # ---------------------------------------------------------------------------------------------------------
