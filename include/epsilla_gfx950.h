@@ -25,6 +25,9 @@
  *                                   order, windowed by skip / limit
  *   eps_index_search_range          (new) every row within a distance of the query - what a filter `@distance < r` asks of a Search - with
  *                                   the count of such rows: the radius query the reference answers by guessing a limit
+ *   eps_index_search_among          the row-by-row loops in which SearchByAttribute judges a primary-key list or a geo index's id list
+ *                                   (db/execution/vec_search_executor.cpp:966-1013), with a distance and a top-k on top: the k closest
+ *                                   of the rows the CALLER names - the allow-list search, the second stage of a hybrid search
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -401,6 +404,26 @@ int32_t eps_index_select(eps_index* h, int64_t skip, int64_t limit, int64_t* ids
  * after an append, a stale bitset / column / attribute rows: EPS_USER_ERROR.  Nothing a later search can observe changes. */
 int32_t eps_index_search_range(eps_index* h, const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p,
                                int64_t* ids_out, float* dist_out, int32_t* counts_out, int64_t* totals_out);
+/* Search among given rows: for every query j the k smallest (distance, id) keys over the VISIBLE rows its candidate list names - the exact k-NN of
+ * an allow list, without a scan of the table and without a bitset of n / 8 bytes.  cand_offsets == NULL: the ONE list cand_ids[0 .. n_cand) serves
+ * every query; else cand_offsets is a HOST int64[nq + 1], non-decreasing, [0] = 0, [nq] = n_cand (anything else: EPS_USER_ERROR), and query j's
+ * list is cand_ids[cand_offsets[j] .. cand_offsets[j + 1]) - two queries of one batch may have different candidate sets.  cand_ids: host (copied
+ * on the index's stream) or device (used in place) int64[n_cand], 0 <= n_cand < 2^31.  Ids are global (eps_index_set_id_map): an id names row
+ * (id - base) / stride; an id that names no row - negative, below base, (id - base) % stride != 0, a row >= eps_index_row_count - is ignored, as
+ * PK2ID returning false is in the reference (:972); a row named several times is judged and returned once.  Visible means not deleted, passing
+ * the int-column test and the installed program, exactly as for eps_index_search; `@distance` reads the row's exact distance.  The distance is,
+ * bit for bit, the value eps_index_search in EPS_MODE_FLAT returns for that (row, query).  counts_out[j] (may be NULL) = min(k, distinct visible
+ * rows of the list), the unused slots -1 / +inf, an empty list: count 0.  queries, ids_out [nq][k], dist_out [nq][k], counts_out [nq]: as for
+ * eps_index_search - host or device, the outputs all of one kind; device: on the index's stream, the caller synchronises; host: the call
+ * synchronises.  1 <= k <= 1024 (a caller who wants more from a list orders it itself); nq = 0: EPS_OK.  A sharded handle:
+ * EPS_DB_UNSUPPORTED_ERROR; after an append, a stale bitset / column / attribute rows: EPS_USER_ERROR.  Two launches (csrc/among.hip): a gather
+ * with the flat scan's blocking that takes its row pointers from the list - m * dim * 4 bytes of rows per 4 queries for a shared list of m
+ * entries, the sum of m_j * dim * 4 for per-query lists, 8 bytes per id - and a merge of the wavefronts' lists that drops repeated keys.
+ * eps_index_last_stats reports the call like a search: dist_evals = (row, query) pairs given a distance (the entries that name a row, times the
+ * queries they serve), main_kernel_bits 32, main_kernel_rows = n_cand, main_kernel_queries = nq, main_kernel_ms = the gather.  Nothing a later
+ * search can observe changes. */
+int32_t eps_index_search_among(eps_index* h, const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand,
+                               int32_t k, int64_t* ids_out, float* dist_out, int32_t* counts_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

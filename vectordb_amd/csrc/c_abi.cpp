@@ -239,6 +239,11 @@ int32_t eps_index_search_range(eps_index* h, const float* q, int64_t nq, const f
   return on_single_device(h, "search_range: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
                           [&](Index& ix) { return ix.search_range(q, nq, radius, cap, p, ids, dist, counts, totals); });
 }
+int32_t eps_index_search_among(eps_index* h, const float* q, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k,
+                               int64_t* ids, float* dist, int32_t* counts) {
+  return on_single_device(h, "search_among: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
+                          [&](Index& ix) { return ix.search_among(q, nq, cand_ids, cand_offsets, n_cand, k, ids, dist, counts); });
+}
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;
   return const_cast<IndexBase*>(CIX(h))->last_stats(out);

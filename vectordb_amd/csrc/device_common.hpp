@@ -334,6 +334,24 @@ struct WaveTopK {
   }
 };
 
+// Every lane with `valid` offers its key to query q's list: the keys below the list's k-th enter one by one (wave-uniform), and only those are
+// judged for visibility.  thr[q] follows the k-th entry.
+template <int NQ, int KPL>
+__device__ __forceinline__ void offer(WaveTopK<KPL> (&list)[NQ], u64 (&thr)[NQ], int q, u64 key, bool valid,
+                                      const FilterSpec& f, int k, bool unique) {
+  u64 m = __ballot(valid && key < thr[q]);
+  while (m) {
+    const int l = __ffsll((long long)m) - 1;
+    m &= m - 1;
+    const u64 x = shfl64(key, l);
+    if (x < thr[q] && row_visible(f, key_id(x), key_dist(x))) {
+      if (unique) list[q].insert_unique(x); else list[q].insert(x);
+      const u64 kth = list[q].entry(k - 1);
+      thr[q] = kth < thr[q] ? kth : thr[q];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Geometry of "G lanes per row": G = smallest power of two with G*4 >= dim (VEC4) or G >= dim (scalar),
 // capped at 64.  RPW = 64 / G rows are evaluated by one wavefront at once.

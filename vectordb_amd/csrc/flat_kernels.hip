@@ -13,22 +13,6 @@
 namespace eps {
 
 // ------------------------------------------------------------------------------------------------
-template <int NQ, int KPL>
-__device__ __forceinline__ void offer(WaveTopK<KPL> (&list)[NQ], u64 (&thr)[NQ], int q, u64 key, bool valid,
-                                      const FilterSpec& f, int k, bool unique) {
-  u64 m = __ballot(valid && key < thr[q]);
-  while (m) {
-    const int l = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    const u64 x = shfl64(key, l);
-    if (x < thr[q] && row_visible(f, key_id(x), key_dist(x))) {
-      if (unique) list[q].insert_unique(x); else list[q].insert(x);
-      const u64 kth = list[q].entry(k - 1);
-      thr[q] = kth < thr[q] ? kth : thr[q];
-    }
-  }
-}
-
 template <int NQ, int KPL, bool VEC4, int U>
 __global__ __launch_bounds__(256) void flat_scan_kernel(FlatScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -89,15 +73,6 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(FlatScanArgs a) {
 #pragma unroll
   for (int q = 0; q < NQ; ++q)
     if (q0 + q < a.nq) list[q].store(a.partial + ((q0 + q) * W + w) * a.k, a.k);
-}
-
-static int pick_kpl(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : k <= 512 ? 8 : 16; }
-static int pick_nq(int64_t nq, int k, int dim) {
-  if (k > 128) return 1;
-  int want = nq >= 3 ? 4 : (nq == 2 ? 2 : 1);
-  // the NQ queries are staged in LDS: keep NQ * dim floats within 64 KB
-  while (want > 1 && (size_t)want * ((dim + 3) & ~3) * sizeof(float) > 65536) want >>= 1;
-  return want;
 }
 
 int flat_scan_waves(int64_t nrows, int64_t nq, int dim) {

@@ -172,6 +172,10 @@ class Index : public IndexBase {
   int32_t search_range(const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* p, int64_t* ids_out, float* dist_out,
                        int32_t* counts_out, int64_t* totals_out);
 
+  // the k closest visible rows among the ids the caller names: one list for the batch, or one per query (eps_index_search_among; among.hip)
+  int32_t search_among(const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k,
+                       int64_t* ids_out, float* dist_out, int32_t* counts_out);
+
   int64_t row_count() const override { return n_rows_; }
 
   // ---- used by the engine translation units
@@ -232,11 +236,15 @@ class Index : public IndexBase {
     size_t cap = 0;
     ~HostBuf();
     bool reserve(size_t bytes);
-  } h_out_, h_q_, h_rng_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
+  } h_out_, h_q_, h_rng_, h_among_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
   DevBuf sel_bits_, sel_scan_, sel_out_;   // select(): visibility bitset; block counts | offsets; [count | total | ids] of a call with host result pointers
   // search_range(): survivor keys [nq][cap]; survivor counts | status | candidates re-ranked (what the host reads back); radii | fall-back query
   // numbers; [ids | distances | counts | totals] of a call with host result pointers.  h_rng_: the page-locked side of the middle two
   DevBuf rng_keys_, rng_cnt_, rng_in_, rng_out_;
+  // search_among(): [pair counter | offsets | a host list's ids].  h_among_: the counter's page-locked copy - the call's dist_evals, read by
+  // last_stats once the call's last event has passed (among_evals_pending_), so that a call with device results stays asynchronous
+  DevBuf among_in_;
+  bool among_evals_pending_ = false;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   // main-kernel event pairs of the last KRING search calls (read back after a run without a sync inside it);
   // evk0_/evk1_ alias the pair of the call in progress

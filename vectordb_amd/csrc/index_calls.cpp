@@ -1,4 +1,4 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, the steps they share, and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, the steps they share, and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
@@ -77,6 +77,7 @@ int32_t Index::check_filters_cover_table(const char* who) {
 void Index::begin_timed_call() {
   std::memset(&stats_, 0, sizeof(stats_));
   stage_n_ = 0;
+  among_evals_pending_ = false;
   kring_seq_ += 1;
   const int slot = (int)(kring_seq_ % KRING);
   evk0_ = kring_[slot][0];
@@ -467,10 +468,108 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
   return EPS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ search_among
+// The k closest visible rows among the ids the caller names (among.hip): gather, merge, result conversion - no host sync of its own, so a call
+// with device results stays asynchronous (the pairs given a distance are counted on the device and read by last_stats).  Reports like a search
+// (statistics, kernel ring); changes nothing a later search can observe.
+int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k, int64_t* ids,
+                            float* dist, int32_t* counts) {
+  if (k < 1 || k > AMONG_MAX_K) return fail(EPS_USER_ERROR, "search_among: k must be in [1, 1024]");
+  HIP_TRY(hipSetDevice(device_));
+  if (cand_offsets && is_device_ptr(cand_offsets)) return fail(EPS_USER_ERROR, "search_among: cand_offsets must be a host array");
+  const char* why;
+  int64_t longest = 0;
+  if (among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_among: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (!queries || !ids || !dist || (n_cand > 0 && !cand_ids)) return fail(EPS_USER_ERROR, "search_among: null buffer");
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)))
+    return fail(EPS_USER_ERROR, "search_among: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  int32_t rc = check_filters_cover_table("search_among");
+  if (rc != EPS_OK) return rc;
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
+
+  const float* dq;
+  rc = stage_queries("search_among", queries, nq, &dq);
+  if (rc != EPS_OK) return rc;
+
+  // ---- scratch: [pair counter | offsets | a host list's ids], partial lists, result keys, host results' device block
+  const bool ids_dev = n_cand > 0 && is_device_ptr(cand_ids);
+  const size_t off_bytes = cand_offsets ? (size_t)(nq + 1) * sizeof(int64_t) : 0, list_bytes = ids_dev ? 0 : (size_t)n_cand * sizeof(int64_t);
+  const AmongPlan plan = among_plan(!cand_offsets, nq, longest, k, pick_nq(nq, k, (int)dim_));
+  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float), out_bytes = ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
+  if (!among_in_.reserve(8 + off_bytes + list_bytes) || !partial_buf_.reserve((size_t)nq * plan.W * k * sizeof(u64)) ||
+      !run_buf_.reserve((size_t)nq * k * sizeof(u64)) || (!out_dev && !out_buf_.reserve(out_bytes)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of device memory (scratch)");
+  if (!h_among_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of page-locked host memory");
+  unsigned long long* d_evals = among_in_.as<unsigned long long>();
+  int64_t* d_off = cand_offsets ? among_in_.as<int64_t>() + 1 : nullptr;
+  const int64_t* d_list = cand_ids;
+  HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
+  if (cand_offsets) HIP_TRY(hipMemcpyAsync(d_off, cand_offsets, off_bytes, hipMemcpyHostToDevice, stream_));
+  if (!ids_dev && n_cand > 0) {
+    d_list = reinterpret_cast<const int64_t*>(among_in_.as<char>() + 8 + off_bytes);
+    HIP_TRY(hipMemcpyAsync(const_cast<int64_t*>(d_list), cand_ids, list_bytes, hipMemcpyHostToDevice, stream_));
+  }
+  u64* run_keys = run_buf_.as<u64>();
+  int64_t* d_ids = ids;
+  float* d_dist = dist;
+  int32_t* d_cnt = counts;
+  if (!out_dev) {
+    d_ids = out_buf_.as<int64_t>();
+    d_dist = reinterpret_cast<float*>(out_buf_.as<char>() + ids_bytes);
+    d_cnt = reinterpret_cast<int32_t*>(out_buf_.as<char>() + ids_bytes + dist_bytes);
+  }
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  stats_.main_kernel_rows = n_cand;
+  stats_.main_kernel_queries = nq;
+  stats_.main_kernel_bits = 32;
+  if (n_cand > 0 && n_rows_ > 0) {
+    AmongArgs a;
+    a.rows = d_rows_;
+    a.n_rows = n_rows_;
+    a.dim = (int)dim_;
+    a.metric = metric_;
+    a.queries = dq;
+    a.nq = nq;
+    a.k = k;
+    a.f = filter_spec();
+    a.ids = d_list;
+    a.offsets = d_off;
+    a.n_cand = n_cand;
+    a.id_base = id_base_;
+    a.id_stride = id_stride_;
+    a.plan = plan;
+    a.partial = partial_buf_.as<u64>();
+    a.evals = d_evals;
+    HIP_TRY(hipEventRecord(evk0_, stream_));
+    launch_among_gather(a, stream_);
+    HIP_TRY(hipEventRecord(evk1_, stream_));
+    launch_among_merge(a.partial, plan.W, k, nq, run_keys, stream_);
+    stats_.main_kernel_launches = 1;
+  } else {   // no list entry can name a row
+    launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
+  }
+  launch_finalize(run_keys, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
+  HIP_TRY(hipMemcpyAsync(h_among_.p, d_evals, 8, hipMemcpyDeviceToHost, stream_));
+  among_evals_pending_ = true;
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(d_ids, out_bytes, {{ids, 0, ids_bytes}, {dist, ids_bytes, dist_bytes}, {counts, ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
 int32_t Index::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   // event timings are read lazily: the caller may have left the work in flight
   if (ev0_ && hipEventSynchronize(ev1_) == hipSuccess) {
+    if (among_evals_pending_) s.dist_evals = (int64_t)*static_cast<const unsigned long long*>(h_among_.p);   // (copied out in front of ev1_)
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) s.kernel_ms = ms;
     if (s.main_kernel_launches > 0 && hipEventElapsedTime(&ms, evk0_, evk1_) == hipSuccess) s.main_kernel_ms = ms;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "among_host.hpp"
 #include "device_common.hpp"
 #include "merge_host.hpp"
 
@@ -25,6 +26,15 @@ struct FlatScanArgs {
   const u64* lo_in;             // optional: only keys > lo_in[q * lo_stride] can enter (paging through results beyond 1024 per query), or null
   int64_t lo_stride;
 };
+// the shape of a scan over k-lists: 64-entry registers per lane of a WaveTopK, queries staged per workgroup (flat_kernels.hip, among.hip)
+inline int pick_kpl(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : k <= 512 ? 8 : 16; }
+inline int pick_nq(int64_t nq, int k, int dim) {
+  if (k > 128) return 1;
+  int want = nq >= 3 ? 4 : (nq == 2 ? 2 : 1);
+  // the NQ queries are staged in LDS: keep NQ * dim floats within 64 KB
+  while (want > 1 && (size_t)want * ((dim + 3) & ~3) * sizeof(float) > 65536) want >>= 1;
+  return want;
+}
 // returns W (partial lists per query). `partial` must hold nq * flat_scan_waves(...) * k keys.
 int flat_scan_waves(int64_t nrows, int64_t nq, int dim);
 void launch_flat_scan(const FlatScanArgs& a, hipStream_t s);
@@ -167,6 +177,27 @@ struct RangeOrderArgs {
 void launch_range_order(const RangeOrderArgs& a, hipStream_t s);
 // the queries named by qsel, copied next to each other (out, may be null); zero_cnt: their survivor counts start again at 0
 void launch_range_gather(const float* queries, int dim, const int32_t* qsel, int64_t m, float* out, u32* cnt, bool zero_cnt, hipStream_t s);
+
+// ---------------------------------------------------------------- search among given rows (eps_index_search_among; among.hip, plan: among_host.hpp)
+struct AmongArgs {
+  const float* rows;
+  int64_t n_rows;            // > 0: an id names row (id - id_base) / id_stride if that is a whole number below n_rows, else no row
+  int dim, metric;
+  const float* queries;      // [nq][dim]
+  int64_t nq;
+  int k;
+  FilterSpec f;
+  const int64_t* ids;        // the lists' entries, global ids
+  const int64_t* offsets;    // [nq + 1] query j's list = ids[offsets[j] .. offsets[j + 1]); null: ids[0 .. n_cand) for every query
+  int64_t n_cand;
+  int64_t id_base, id_stride;
+  AmongPlan plan;
+  u64* partial;              // [nq][plan.W][k] per-wavefront sorted lists of unique keys
+  unsigned long long* evals; // [1] += (row, query) pairs given a distance
+};
+// the gather (in slices of AMONG_GRID_Y query tiles), then the merge of every query's partial lists into run_keys[nq][k]: sorted, unique
+void launch_among_gather(const AmongArgs& a, hipStream_t s);
+void launch_among_merge(const u64* partial, int W, int k, int64_t nq, u64* run_keys, hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch

@@ -427,6 +427,53 @@ class GpuIndex:
                                                   _ptr(totals)))
         return ids, dist, counts, totals
 
+    def search_among(self, queries, ids, k, offsets=None, out=None):
+        """eps_index_search_among: per query the k closest VISIBLE rows among the ids the caller names (global ids, eps_index_set_id_map; an id
+        that names no row is ignored, a row named several times counts once).  ids: int64, NumPy or a device tensor - offsets None: ONE list for
+        every query; else any integer sequence of nq + 1 non-decreasing positions, offsets[0] = 0, offsets[nq] = len(ids): query j's list is
+        ids[offsets[j]:offsets[j + 1]].  Returns (ids int64[nq, k], dist float32[nq, k], counts int32[nq]) in ascending (distance, id) order, the
+        rest -1 / +inf; the distances are a flat search's, bit for bit.  NumPy queries give NumPy results; device queries give device tensors
+        and the call is asynchronous on the index's stream.  out=(ids, dist, counts): caller-provided buffers, all NumPy or all device."""
+        k = int(k)
+        dev = _is_dev(queries)
+        if not dev:
+            queries = np.ascontiguousarray(queries, np.float32)
+            if queries.ndim == 1:
+                queries = queries[None, :]
+        nq = queries.shape[0]
+        assert queries.shape[1] == self.dim
+        if _is_dev(ids):
+            if str(ids.dtype) != "torch.int64" or ids.dim() != 1 or not ids.is_contiguous():
+                raise ValueError("search_among: device ids must be a contiguous 1-D int64 tensor, got %s %s" % (ids.dtype, tuple(ids.shape)))
+            n_cand = ids.numel()
+        else:
+            ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            n_cand = ids.size
+        if offsets is not None:
+            offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_dev(offsets) else offsets), np.int64).reshape(-1)
+            if offsets.size != nq + 1:
+                raise ValueError("search_among: offsets must hold nq + 1 = %d entries, got %d" % (nq + 1, offsets.size))
+        if out is not None:
+            out_ids, dist, counts = out
+            if len({_is_dev(a) for a in out}) != 1:
+                raise ValueError("search_among: out[ids], out[dist] and out[counts] must all be NumPy arrays or all be device tensors")
+            _check_out(out_ids, "ids", (nq, k), "int64")
+            _check_out(dist, "dist", (nq, k), "float32")
+            _check_out(counts, "counts", (nq,), "int32")
+        elif dev:
+            import torch
+            out_ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
+            dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=queries.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+        else:
+            out_ids = np.empty((nq, max(k, 0)), np.int64)
+            dist = np.empty((nq, max(k, 0)), np.float32)
+            counts = np.empty(nq, np.int32)
+        self._keep["among"] = (queries, ids, offsets)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_among(self.h, _ptr(queries), nq, _ptr(ids) if n_cand else None, _ptr(offsets), n_cand, k, _ptr(out_ids),
+                                                  _ptr(dist), _ptr(counts)))
+        return out_ids, dist, counts
+
     def kernel_times(self, cap=64):
         """main-kernel ms of the most recent search calls (oldest first); synchronises the index's stream"""
         buf = (C.c_double * cap)()
