@@ -1,4 +1,4 @@
-"""CPU: the occupancy bound the device traversal lays its worker queues out with (csrc/traverse.hip, r6).
+"""CPU: the occupancy bound the device traversal lays its worker queues out with (trv_queues, csrc/graph_host.hpp; r6).
 
 Between two MergeAllQueuesToMaster calls (engine/db/execution/vec_search_executor.cpp:297-326, which empty the worker queues) a worker's queue holds
 its share of the master's unchecked candidates - PickTopMToWorkers (:328-356) deals them round-robin, every T-th stays with the master: at most

@@ -361,6 +361,13 @@ __host__ __device__ inline int group_lanes(int64_t dim, bool vec4) {
   while (g < 64 && g < need) g <<= 1;
   return g;
 }
+// fp32 rounding of a row distance that the traversals' 8-bit prefilter compares with its bound: G lanes x (dim / G) sequential fmas + a
+// log2(G)-level tree
+inline float prefilter_slack(int64_t dim, int G) {
+  const float terms = (float)((dim + G - 1) / G) + 6.f;
+  const float slack = 2.f * (3.f * terms + 6.f) * 5.9604645e-8f;
+  return slack > 8e-6f ? slack : 8e-6f;
+}
 
 // Accumulate U rows x NQ queries.  rowp[u] points at the row for this lane's group (already clamped to
 // a valid row); qs = LDS copy of the NQ queries, each dim floats (16-B aligned when VEC4).

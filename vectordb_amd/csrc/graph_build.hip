@@ -25,12 +25,14 @@
 #include <cstring>
 #include <vector>
 
+#include "graph_host.hpp"
 #include "index.hpp"
 #include "traverse_kernel.hpp"
 
 namespace eps {
 
 constexpr int PRUNE_POOL = 4096;   // sorted candidate pool per node (LDS)
+constexpr int GHASH_SLOTS = 32768; // visited hash slots per search of Link / connectivity in HBM (BuildCtx::link_stage)
 
 // ------------------------------------------------------------------------------------------------ kNN extraction
 __global__ void knn_extract_kernel(const u64* run_keys, int k1, int64_t q0, int64_t nq, int K, u32* knn_ids) {
@@ -375,7 +377,7 @@ static int32_t inter_insert_device(Index& ix, const u32* nsg_ids, const float* n
                                    DevBuf& out_dist, DevBuf& out_deg) {
   hipStream_t s = ix.stream_;
   const int dim = (int)ix.dim_;
-  const bool vec4 = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(ix.d_rows_) & 15) == 0);
+  const bool vec4 = rows_vec4(ix.d_rows_, dim);
   const size_t prn_shm = prune_lds_bytes(dim, R);
   DevBuf rev_ids, rev_dist, rev_cnt, rev_off;
   if (!rev_cnt.reserve((size_t)n * 4) || !rev_off.reserve((size_t)(n + 1) * 8) || !out_ids.reserve((size_t)n * R * 4) ||
@@ -425,48 +427,74 @@ static int32_t inter_insert_device(Index& ix, const u32* nsg_ids, const float* n
   return EPS_OK;
 }
 
-int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const BuildStage* hook) {
-  hipStream_t s = ix.stream_;
-  const int dim = (int)ix.dim_;
-  if (n <= 1) {
-    if (hook && hook->stop_after) return ix.fail(EPS_USER_ERROR, "build stage: need at least two rows");
-    std::vector<int64_t> off((size_t)n + 1, 0), nbr;
-    return ix.set_graph(n, off.data(), nbr.data(), 0);
-  }
-  const int K = (int)std::min<int64_t>(bp.knng, n - 1);
-  const int R = (int)bp.out_degree;
-  const int Ls = (int)std::min<int64_t>(bp.search_length, n);
-  if (K <= 0 || R <= 0 || Ls <= 0 || K + 1 > 1024 || R > 512)
-    return ix.fail(EPS_USER_ERROR, "build: unsupported parameters (need 0 < knng < 1024, 0 < out_degree <= 512)");
-  const bool vec4 = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(ix.d_rows_) & 15) == 0);
-  const bool debug = tune_env("EPS_DEBUG") != nullptr;
-  struct EventPair {   // released on every return path
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evp;
-  HIPCHK(hipEventCreate(&evp.a));
-  HIPCHK(hipEventCreate(&evp.b));
-  hipEvent_t e0 = evp.a, e1 = evp.b;
-  auto lap = [&](const char* what) {
-    if (!debug) return;
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    fprintf(stderr, "[eps build] %-28s %10.2f ms\n", what, ms);
-    (void)hipEventRecord(e0, s);
-  };
-  (void)hipEventRecord(e0, s);
+static_assert(TRACE_EMPTY == KEY_EMPTY && TRV_NONE == 0xFFFFFFFFu, "graph_host.hpp reads the kernels' keys and list padding");
 
-  // ---- 1. kNN graph (KNNGraph / NN-Descent in the reference, knn.hpp:90-135, nndescent.hpp:96-192: approximate there).
-  // Below 65 536 rows: exact stream scan.  Above: every block of B rows goes through the matrix filter in its approximate-key
-  // mode (8-bit operands, r3), which selects the kA = 128 closest rows by approximate key, and those 128 are re-ranked in exact
-  // fp32 - the lists are the exact K nearest unless a true neighbour's approximate rank falls beyond 128 (the approximate key's
-  // error is a small fraction of the gap between the K-th and the 128-th neighbour; tests/test_gpu_build.py measures the recall).
-  DevBuf knn, run, runA, candA, cntA;
+// What the stages of one build share: its sizes, the debug lap timer, and the device buffers that outlive a stage.
+struct BuildCtx {
+  Index& ix;
+  const eps_build_params& bp;
+  const BuildStage* hook;
+  const int64_t n;
+  const int dim, K, R, Ls;
+  const bool vec4, debug;
+  hipStream_t s;
+  hipEvent_t e0 = nullptr, e1 = nullptr;   // lap timer
+  DevBuf knn, run;                         // kNN lists u32 [n][K]; result keys of the stages' flat scans
+  int64_t nav = 0;
+  // the searches of Link and of the connectivity stage: seeds, logs, counters, visited sets, the batch on the mirror's grid
+  DevBuf d_seeds, logb, logc, counters, visb, q8b, qstat8b;
+  bool bitmap_vis = false, ghash_vis = false, prefilter = false;
+  int64_t vis_words = 0, NB = 0;           // searches per batch
+  int Lcap = 0;
+  size_t trv_shm = 0, trv_shm_bm = 0;
+  Quant8View q8v;
+  TraverseArgs ta;
+  DevBuf nsg_ids, nsg_dist, nsg_deg;       // what Link leaves: u32 [n][R], float [n][R], u32 [n]
+  DevBuf out_ids, out_dist, out_deg;       // ... and InterInsert
+  std::vector<u32> h_ids, h_deg;           // InterInsert's lists on the host (connectivity_stage)
+
+  BuildCtx(Index& ix_, int64_t n_, const eps_build_params& bp_, const BuildStage* hook_)
+      : ix(ix_), bp(bp_), hook(hook_), n(n_), dim((int)ix_.dim_), K((int)std::min<int64_t>(bp_.knng, n_ - 1)), R((int)bp_.out_degree),
+        Ls((int)std::min<int64_t>(bp_.search_length, n_)), vec4(rows_vec4(ix_.d_rows_, ix_.dim_)), debug(tune_env("EPS_DEBUG") != nullptr), s(ix_.stream_) {}
+  ~BuildCtx() {   // released on every return path
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  int32_t start_timer();
+  void lap(const char* what);
+  int32_t knn_stage();
+  int32_t export_knn();
+  int32_t navigation_stage();
+  int32_t link_stage();
+  hipError_t launch_link_search(int64_t nb);
+  int32_t export_link();
+  int32_t link_report();
+  int32_t connectivity_stage(std::vector<std::pair<u32, u32>>* extra, size_t* n_orphans);
+};
+
+int32_t BuildCtx::start_timer() {
+  HIPCHK(hipEventCreate(&e0));
+  HIPCHK(hipEventCreate(&e1));
+  (void)hipEventRecord(e0, s);
+  return EPS_OK;
+}
+void BuildCtx::lap(const char* what) {
+  if (!debug) return;
+  (void)hipEventRecord(e1, s);
+  (void)hipEventSynchronize(e1);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  fprintf(stderr, "[eps build] %-28s %10.2f ms\n", what, ms);
+  (void)hipEventRecord(e0, s);
+}
+
+// ---- 1. kNN graph (KNNGraph / NN-Descent in the reference, knn.hpp:90-135, nndescent.hpp:96-192: approximate there).
+// Below 65 536 rows: exact stream scan.  Above: every block of B rows goes through the matrix filter in its approximate-key
+// mode (8-bit operands, r3), which selects the kA = 128 closest rows by approximate key, and those 128 are re-ranked in exact
+// fp32 - the lists are the exact K nearest unless a true neighbour's approximate rank falls beyond 128 (the approximate key's
+// error is a small fraction of the gap between the K-th and the 128-th neighbour; tests/test_gpu_build.py measures the recall).
+int32_t BuildCtx::knn_stage() {
+  DevBuf runA, candA, cntA;
   const int k1 = K + 1;
   constexpr int64_t B = 2048;   // queries per kNN pass
   const bool use_mfma = n >= 65536;
@@ -481,7 +509,11 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   } else {
     if (use_mfma && (!runA.reserve((size_t)B * kA * 8) || !candA.reserve((size_t)B * kA * 4) || !cntA.reserve((size_t)B * 4)))
       return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (kNN graph)");
-    ix.scan_limit_ = n;  // the graph covers rows [0,n) only
+    struct ScanLimit {   // the graph covers rows [0,n) only; lifted again on every way out
+      Index& ix;
+      ScanLimit(Index& i, int64_t n) : ix(i) { ix.scan_limit_ = n; }
+      ~ScanLimit() { ix.scan_limit_ = -1; }
+    } limit(ix, n);
     for (int64_t q0 = 0; q0 < n; q0 += B) {
       const int64_t nq = std::min(B, n - q0);
       const float* dq = ix.d_rows_ + q0 * dim;
@@ -509,26 +541,26 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
       } else {
         rc = ix.flat_stream(dq, nq, k1, 0, n, run.as<u64>(), -1, false);
       }
-      if (rc != EPS_OK) {
-        ix.scan_limit_ = -1;
-        return rc;
-      }
+      if (rc != EPS_OK) return rc;
       hipLaunchKernelGGL(knn_extract_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, run.as<u64>(), k1, q0, nq, K,
                          knn.as<u32>());
     }
-    ix.scan_limit_ = -1;
   }
   lap("kNN graph");
-  if (hook && hook->stop_after == 1) {
-    DevBuf tmp;
-    if (!tmp.reserve((size_t)n * K * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (kNN graph)");
-    hipLaunchKernelGGL(knn_export_kernel, dim3((unsigned)(((int64_t)n * K + 255) / 256)), dim3(256), 0, s, knn.as<u32>(), (int64_t)n * K, tmp.as<int64_t>());
-    HIPCHK(hipMemcpyAsync(hook->out_ids, tmp.p, (size_t)n * K * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return EPS_OK;
-  }
+  return EPS_OK;
+}
 
-  // ---- 2. navigation node: closest row to the centroid (always L2)
+int32_t BuildCtx::export_knn() {   // stage exit: the kNN lists as int64 [n][K], -1 padded
+  DevBuf tmp;
+  if (!tmp.reserve((size_t)n * K * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (kNN graph)");
+  hipLaunchKernelGGL(knn_export_kernel, dim3((unsigned)(((int64_t)n * K + 255) / 256)), dim3(256), 0, s, knn.as<u32>(), (int64_t)n * K, tmp.as<int64_t>());
+  HIPCHK(hipMemcpyAsync(hook->out_ids, tmp.p, (size_t)n * K * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return EPS_OK;
+}
+
+// ---- 2. navigation node: closest row to the centroid (always L2)
+int32_t BuildCtx::navigation_stage() {
   DevBuf cen;
   if (!cen.reserve((size_t)dim * 4 + 64)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory");
   HIPCHK(hipMemsetAsync(cen.p, 0, (size_t)dim * 4, s));
@@ -542,31 +574,41 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   u64 navkey = 0;
   HIPCHK(hipMemcpyAsync(&navkey, run.p, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  const int64_t nav = (hook && hook->nav_in >= 0 && hook->nav_in < n) ? hook->nav_in : (int64_t)key_id(navkey);
+  nav = (hook && hook->nav_in >= 0 && hook->nav_in < n) ? hook->nav_in : (int64_t)key_id(navkey);
   lap("navigation node");
+  return EPS_OK;
+}
 
-  // seeds of every Link search: the first Ls kNN entries of nav (GetNeighbors, nsg.cpp:174-195), then nav+1, ...
-  std::vector<u32> seeds;
-  {
-    std::vector<u32> row((size_t)K);
-    HIPCHK(hipMemcpyAsync(row.data(), knn.as<u32>() + nav * K, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<uint8_t> sel((size_t)n, 0);
-    for (int i = 0; i < K && (int)seeds.size() < Ls; ++i)
-      if (row[i] != TRV_NONE && !sel[row[i]]) {
-        sel[row[i]] = 1;
-        seeds.push_back(row[i]);
-      }
-    int64_t tmp = nav + 1;
-    while ((int)seeds.size() < Ls) {
-      if (tmp >= n) tmp = 0;
-      const int64_t v = tmp++;
-      if (sel[v]) continue;
-      sel[v] = 1;
-      seeds.push_back((u32)v);
+// one search per block of ta's launch, over the visited set the build runs with (link_stage)
+hipError_t BuildCtx::launch_link_search(int64_t nb) {
+  if (bitmap_vis) {   // exact visited set: one n-bit bitmap per search of the batch, zeroed per batch
+    hipError_t e = hipMemsetAsync(visb.p, 0, (size_t)nb * vis_words * 4, s);
+    if (e != hipSuccess) return e;
+    if (vec4)
+      hipLaunchKernelGGL((traverse_kernel<true, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+    else
+      hipLaunchKernelGGL((traverse_kernel<false, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+  } else {
+    const size_t shm = ghash_vis ? trv_shm_bm : trv_shm;   // (the LDS layout without the table)
+    if (ghash_vis) {
+      hipError_t e = hipMemsetAsync(visb.p, 0xFF, (size_t)nb * GHASH_SLOTS * 4, s);   // TRV_NONE in every slot
+      if (e != hipSuccess) return e;
     }
+    if (vec4)
+      hipLaunchKernelGGL((traverse_kernel<true, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
+    else
+      hipLaunchKernelGGL((traverse_kernel<false, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
   }
-  DevBuf d_seeds, logb, logc, counters, nsg_ids, nsg_dist, nsg_deg, visb;
+  return hipSuccess;
+}
+
+// ---- 3. Link: per node a search on the kNN graph from the navigation node, then SelectEdge over what it evaluated + the node's kNN list
+int32_t BuildCtx::link_stage() {
+  // seeds of every Link search: the first Ls kNN entries of nav (GetNeighbors, nsg.cpp:174-195), then nav+1, ...
+  std::vector<u32> seeds, row((size_t)K);
+  HIPCHK(hipMemcpyAsync(row.data(), knn.as<u32>() + nav * K, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  seed_list(row.data(), K, nav, n, Ls, seeds);
   // visited set of the Link / connectivity searches (the reference's has_calculated bitset, n bits per search):
   //   default        a hash table of 32768 slots per search in HBM (128 KB: the ~1000 searches in flight keep theirs in L2 /
   //                  Infinity Cache), reset per batch of 16384 searches; a search that fills 3/4 of it stops discovering -
@@ -576,11 +618,10 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   //   EPS_BUILD_VISITED=lds      the r1 table of 8192 slots in LDS: a third of the searches at 1M x 768 fill it (5.4 k
   //                  evaluations instead of 5.8 k); same recall
   const char* vis_env = tune_env("EPS_BUILD_VISITED");
-  const bool bitmap_vis = vis_env && std::strcmp(vis_env, "bitmap") == 0;
-  const bool ghash_vis = !bitmap_vis && !(vis_env && std::strcmp(vis_env, "lds") == 0);
-  constexpr int GHASH_SLOTS = 32768;
-  const int64_t vis_words = (n + 31) / 32;
-  int64_t NB = std::min<int64_t>(n, 16384);
+  bitmap_vis = vis_env && std::strcmp(vis_env, "bitmap") == 0;
+  ghash_vis = !bitmap_vis && !(vis_env && std::strcmp(vis_env, "lds") == 0);
+  vis_words = (n + 31) / 32;
+  NB = std::min<int64_t>(n, 16384);
   if (bitmap_vis) NB = std::max<int64_t>(256, std::min<int64_t>(NB, ((int64_t)2 << 30) / (vis_words * 4)));
   if (bitmap_vis && !visb.reserve((size_t)NB * vis_words * 4)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (visited bitmaps)");
   if (ghash_vis && !visb.reserve((size_t)NB * GHASH_SLOTS * 4)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory (visited tables)");
@@ -597,22 +638,19 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   while (Lp2 < Ls || (bp.candidate_pool_size > 0 && Lp2 < bp.candidate_pool_size)) Lp2 <<= 1;
   if (bp.candidate_pool_size <= 0 || Lp2 > 2048) Lp2 = 2048;   // (unlimited depth: the 2048 closest)
   if (Lp2 < Ls) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, "build: search_length > 2048 is not supported");
-  const int Lcap = Lp2;
+  Lcap = Lp2;
   // 8-bit lower-bound prefilter of the searches' distance step (traverse_kernel.hpp, step 3a): the mirror is the one the kNN stage
   // just scanned; EPS_BUILD_PREFILTER=0 turns it off (A/B - the graph is the same either way)
-  Quant8View q8v;
-  bool prefilter = dim >= 128;
+  prefilter = dim >= 128;
   if (const char* e = tune_env("EPS_BUILD_PREFILTER")) prefilter = atoi(e) != 0;
-  DevBuf q8b, qstat8b;
   if (prefilter) {
     const int32_t rc = quant8_view(ix, &q8v);
     if (rc != EPS_OK) q8v = Quant8View();   // (optional: without the mirror the searches read the fp32 rows, the graph is the same)
     prefilter = q8v.x8 != nullptr;
   }
-  const size_t trv_shm = traverse_lds_bytes(dim, Lp2, true, prefilter, q8v.cols8);
-  const size_t trv_shm_bm = traverse_lds_bytes(dim, Lp2, false, prefilter, q8v.cols8);
+  trv_shm = traverse_lds_bytes(dim, Lp2, true, prefilter, q8v.cols8);
+  trv_shm_bm = traverse_lds_bytes(dim, Lp2, false, prefilter, q8v.cols8);
   const size_t prn_shm = prune_lds_bytes(dim, R);
-  TraverseArgs ta;
   ta.rows = ix.d_rows_;
   ta.dim = dim;
   ta.metric = 0;
@@ -641,10 +679,7 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   ta.d_pad8 = q8v.d_pad8;
   ta.cols8 = q8v.cols8;
   ta.u8 = q8v.u;
-  {
-    const int G = group_lanes(dim, vec4);
-    ta.slack8 = std::max(8e-6f, 2.f * (3.f * ((float)((dim + G - 1) / G) + 6.f) + 6.f) * 5.9604645e-8f);
-  }
+  ta.slack8 = prefilter_slack(dim, group_lanes(dim, vec4));
   if (prefilter) {
     if (!q8b.reserve((size_t)NB * q8v.d_pad8) || !qstat8b.reserve((size_t)NB * 16)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory");
     ta.x8 = q8v.x8;
@@ -665,28 +700,6 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   pa.out_ids = nsg_ids.as<u32>();
   pa.out_dist = nsg_dist.as<float>();
   pa.out_deg = nsg_deg.as<u32>();
-  // ---- 3. Link
-  auto launch_link_search = [&](int64_t nb) -> hipError_t {
-    if (bitmap_vis) {   // exact visited set: one n-bit bitmap per search of the batch, zeroed per batch
-      hipError_t e = hipMemsetAsync(visb.p, 0, (size_t)nb * vis_words * 4, s);
-      if (e != hipSuccess) return e;
-      if (vec4)
-        hipLaunchKernelGGL((traverse_kernel<true, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
-      else
-        hipLaunchKernelGGL((traverse_kernel<false, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
-    } else {
-      const size_t shm = ghash_vis ? trv_shm_bm : trv_shm;   // (the LDS layout without the table)
-      if (ghash_vis) {
-        hipError_t e = hipMemsetAsync(visb.p, 0xFF, (size_t)nb * GHASH_SLOTS * 4, s);   // TRV_NONE in every slot
-        if (e != hipSuccess) return e;
-      }
-      if (vec4)
-        hipLaunchKernelGGL((traverse_kernel<true, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
-      else
-        hipLaunchKernelGGL((traverse_kernel<false, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
-    }
-    return hipSuccess;
-  };
   for (int64_t v0 = 0; v0 < n; v0 += NB) {
     const int64_t nb = std::min(NB, n - v0);
     ta.queries = ix.d_rows_ + v0 * dim;
@@ -713,88 +726,47 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   }
   HIPCHK(hipGetLastError());
   lap("Link (search + SelectEdge)");
-  if (hook && hook->stop_after == 2) {   // what Link leaves: per node <= R edges, before InterInsert
-    std::vector<u32> li((size_t)n * R), ld((size_t)n);
-    HIPCHK(hipMemcpyAsync(li.data(), nsg_ids.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ld.data(), nsg_deg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int64_t v = 0; v < n; ++v) {
-      hook->out_deg[v] = (int32_t)ld[v];
-      for (int j = 0; j < R; ++j) hook->out_ids[v * R + j] = j < (int)ld[v] ? (int64_t)li[(size_t)v * R + j] : -1;
-    }
-    if (hook->nav_out) *hook->nav_out = nav;
-    return EPS_OK;
-  }
-  if (debug) {
-    unsigned long long hcnt[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(hcnt, counters.p, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    fprintf(stderr, "[eps build] Link: %.0f evaluations, %.1f expansions per search; queue of %d kept as the pool; visited set: %s, %llu searches filled it\n",
-            (double)hcnt[0] / (double)n, (double)hcnt[1] / (double)n, Lcap, bitmap_vis ? "bitmap" : (ghash_vis ? "hash of 32768 in HBM" : "hash of 8192 in LDS"), hcnt[2]);
-    if (prefilter) fprintf(stderr, "[eps build] Link: 8-bit prefilter on, %.0f neighbour evaluations per search read the fp32 row\n", (double)hcnt[3] / (double)n);
-  }
+  return EPS_OK;
+}
 
-  // ---- 4. InterInsert
-  DevBuf out_ids, out_dist, out_deg;
-  {
-    const int32_t rc = inter_insert_device(ix, nsg_ids.as<u32>(), nsg_dist.as<float>(), nsg_deg.as<u32>(), n, R, out_ids, out_dist, out_deg);
-    if (rc != EPS_OK) return rc;
-  }
-  lap("InterInsert");
+int32_t BuildCtx::export_link() {   // stage exit: what Link leaves, per node <= R edges, before InterInsert
+  std::vector<u32> li((size_t)n * R), ld((size_t)n);
+  HIPCHK(hipMemcpyAsync(li.data(), nsg_ids.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ld.data(), nsg_deg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  lists_to_abi(li.data(), ld.data(), n, R, hook->out_ids, hook->out_deg);
+  if (hook->nav_out) *hook->nav_out = nav;
+  return EPS_OK;
+}
 
-  // ---- 5. connectivity on the host
-  std::vector<u32> h_ids((size_t)n * R), h_deg((size_t)n);
+int32_t BuildCtx::link_report() {   // EPS_DEBUG: the counters of Link's searches
+  if (!debug) return EPS_OK;
+  unsigned long long hcnt[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(hcnt, counters.p, 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  fprintf(stderr, "[eps build] Link: %.0f evaluations, %.1f expansions per search; queue of %d kept as the pool; visited set: %s, %llu searches filled it\n",
+          (double)hcnt[0] / (double)n, (double)hcnt[1] / (double)n, Lcap, bitmap_vis ? "bitmap" : (ghash_vis ? "hash of 32768 in HBM" : "hash of 8192 in LDS"), hcnt[2]);
+  if (prefilter) fprintf(stderr, "[eps build] Link: 8-bit prefilter on, %.0f neighbour evaluations per search read the fp32 row\n", (double)hcnt[3] / (double)n);
+  return EPS_OK;
+}
+
+// ---- 5. connectivity: reachability over InterInsert's lists on the host, one device search per unreached node (Link's search setup, over
+// those lists), then the repair edges (repair_orphans, graph_host.hpp)
+int32_t BuildCtx::connectivity_stage(std::vector<std::pair<u32, u32>>* extra, size_t* n_orphans) {
+  h_ids.resize((size_t)n * R);
+  h_deg.resize((size_t)n);
   HIPCHK(hipMemcpyAsync(h_ids.data(), out_ids.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(h_deg.data(), out_deg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   std::vector<uint8_t> reached((size_t)n, 0);
-  {
-    std::vector<u32> stack;
-    stack.push_back((u32)nav);
-    reached[nav] = 1;
-    while (!stack.empty()) {
-      const u32 x = stack.back();
-      stack.pop_back();
-      for (u32 j = 0; j < h_deg[x]; ++j) {
-        const u32 y = h_ids[(size_t)x * R + j];
-        if (!reached[y]) {
-          reached[y] = 1;
-          stack.push_back(y);
-        }
-      }
-    }
-  }
-  std::vector<u32> orphans;
+  std::vector<u32> stack, orphans;
+  mark_reached((u32)nav, h_ids.data(), h_deg.data(), R, reached, stack);
   for (int64_t i = 0; i < n; ++i)
     if (!reached[i]) orphans.push_back((u32)i);
-  // FindUnconnectedNode (nsg.cpp:734-775): the lowest-id unreached node x gets an in-edge from the closest REACHED node
-  // of a search for V[x]; the DFS then continues through x, so only one node per unreached component receives an
-  // extra edge.  Here the searches of all initially unreached nodes run as one device batch (their 32 closest
-  // evaluated nodes are kept), and the attach + DFS-continue loop runs on the host in id order against the live
-  // `reached` set.
-  constexpr int TRACE_K = 32;
-  std::vector<std::pair<u32, u32>> extra;   // (root, orphan) edges
-  const size_t n_orphans = orphans.size();
+  *n_orphans = orphans.size();
   if (!orphans.empty()) {
     std::vector<u32> nseeds;
-    {
-      std::vector<uint8_t> sel((size_t)n, 0);
-      for (u32 j = 0; j < h_deg[nav] && (int)nseeds.size() < Ls; ++j) {
-        const u32 y = h_ids[(size_t)nav * R + j];
-        if (!sel[y]) {
-          sel[y] = 1;
-          nseeds.push_back(y);
-        }
-      }
-      int64_t tmp = nav + 1;
-      while ((int)nseeds.size() < Ls) {
-        if (tmp >= n) tmp = 0;
-        const int64_t v = tmp++;
-        if (sel[v]) continue;
-        sel[v] = 1;
-        nseeds.push_back((u32)v);
-      }
-    }
+    seed_list(h_ids.data() + (size_t)nav * R, h_deg[nav], nav, n, Ls, nseeds);
     DevBuf d_orph, d_q, d_top;
     const int64_t m = (int64_t)orphans.size();
     const int64_t OB = std::min<int64_t>(m, NB);
@@ -816,75 +788,47 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
       HIPCHK(hipMemcpyAsync(top.data() + (size_t)o0 * TRACE_K, d_top.p, (size_t)nb * TRACE_K * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
     }
-    // Out-degree stays <= 64 (the reference has no cap: on hub-prone data its repair edges pile up on a few nodes -
-    // 291 edges on one node at 1M x 768): a saturated node passes the orphan on to the next closest reached node of the
-    // trace, so every adjacency list keeps the fixed 256-byte stride the traversal kernel reads with one row fetch.
-    const u32 deg_cap = (u32)std::max(64, R + 1);
-    std::vector<u32> live_extra((size_t)n, 0);
-    std::vector<u32> stack;
-    uint64_t lcg = bp.seed ? bp.seed : 100;
-    for (int64_t i = 0; i < m; ++i) {
-      const u32 x = orphans[i];
-      if (reached[x]) continue;   // linked through an earlier orphan's subtree
-      int64_t root = -1;
-      for (int e = 0; e < TRACE_K; ++e) {
-        const u64 key = top[(size_t)i * TRACE_K + e];
-        if (key == KEY_EMPTY) break;
-        const u32 c = key_id(key);
-        if (reached[c] && h_deg[c] + live_extra[c] < deg_cap) {
-          root = c;
-          break;
-        }
-      }
-      while (root < 0) {          // a random linked node (nsg.cpp:763-771), here one that still has room
-        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-        const u32 c = (u32)((lcg >> 33) % (uint64_t)n);
-        if (reached[c] && h_deg[c] + live_extra[c] < deg_cap) root = c;
-      }
-      live_extra[root]++;
-      extra.emplace_back((u32)root, x);
-      reached[x] = 1;
-      stack.push_back(x);
-      while (!stack.empty()) {
-        const u32 v = stack.back();
-        stack.pop_back();
-        for (u32 j = 0; j < h_deg[v]; ++j) {
-          const u32 y = h_ids[(size_t)v * R + j];
-          if (!reached[y]) {
-            reached[y] = 1;
-            stack.push_back(y);
-          }
-        }
-      }
-    }
+    *extra = repair_orphans(n, R, h_ids.data(), h_deg.data(), orphans, top.data(), reached, (u32)std::max(64, R + 1), bp.seed ? bp.seed : 100);
   }
   lap("connectivity");
-
-  // ---- CSR in the reference's layout (ann_graph_segment.cpp:222-241)
-  std::vector<int64_t> off((size_t)n + 1);
-  std::vector<u32> extra_cnt((size_t)n, 0);
-  for (auto& pr : extra) extra_cnt[pr.first]++;
-  int64_t e = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    off[i] = e;
-    e += h_deg[i] + extra_cnt[i];
-  }
-  off[n] = e;
-  std::vector<int64_t> nbr((size_t)e);
-  std::vector<int64_t> fill((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    for (u32 j = 0; j < h_deg[i]; ++j) nbr[off[i] + j] = h_ids[(size_t)i * R + j];
-    fill[i] = off[i] + h_deg[i];
-  }
-  for (auto& pr : extra) nbr[fill[pr.first]++] = pr.second;
-  if (debug) {
-    u32 maxdeg = 0;
-    for (int64_t i = 0; i < n; ++i) maxdeg = std::max(maxdeg, h_deg[i] + extra_cnt[i]);
-    fprintf(stderr, "[eps build] n=%lld edges=%lld avg degree %.1f max degree %u, %zu nodes unreached after InterInsert, %zu repair edges, nav %lld\n",
-            (long long)n, (long long)e, (double)e / n, maxdeg, n_orphans, extra.size(), (long long)nav);
-  }
-  return ix.set_graph(n, off.data(), nbr.data(), nav);
+  return EPS_OK;
 }
+
+int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const BuildStage* hook) {
+  if (n <= 1) {
+    if (hook && hook->stop_after) return ix.fail(EPS_USER_ERROR, "build stage: need at least two rows");
+    std::vector<int64_t> off((size_t)n + 1, 0), nbr;
+    return ix.set_graph(n, off.data(), nbr.data(), 0);
+  }
+  BuildCtx c(ix, n, bp, hook);
+  if (c.K <= 0 || c.R <= 0 || c.Ls <= 0 || c.K + 1 > 1024 || c.R > 512)
+    return ix.fail(EPS_USER_ERROR, "build: unsupported parameters (need 0 < knng < 1024, 0 < out_degree <= 512)");
+  int32_t rc;
+  if ((rc = c.start_timer()) != EPS_OK) return rc;
+  if ((rc = c.knn_stage()) != EPS_OK) return rc;
+  if (hook && hook->stop_after == 1) return c.export_knn();
+  if ((rc = c.navigation_stage()) != EPS_OK) return rc;
+  if ((rc = c.link_stage()) != EPS_OK) return rc;
+  if (hook && hook->stop_after == 2) return c.export_link();
+  if ((rc = c.link_report()) != EPS_OK) return rc;
+  // ---- 4. InterInsert
+  rc = inter_insert_device(ix, c.nsg_ids.as<u32>(), c.nsg_dist.as<float>(), c.nsg_deg.as<u32>(), n, c.R, c.out_ids, c.out_dist, c.out_deg);
+  if (rc != EPS_OK) return rc;
+  c.lap("InterInsert");
+  std::vector<std::pair<u32, u32>> extra;   // (root, orphan) repair edges
+  size_t n_orphans = 0;
+  if ((rc = c.connectivity_stage(&extra, &n_orphans)) != EPS_OK) return rc;
+  std::vector<int64_t> off, nbr;
+  graph_csr(n, c.R, c.h_ids.data(), c.h_deg.data(), extra, off, nbr);
+  if (c.debug) {
+    int64_t maxdeg = 0;
+    for (int64_t i = 0; i < n; ++i) maxdeg = std::max(maxdeg, off[i + 1] - off[i]);
+    fprintf(stderr, "[eps build] n=%lld edges=%lld avg degree %.1f max degree %lld, %zu nodes unreached after InterInsert, %zu repair edges, nav %lld\n",
+            (long long)n, (long long)off[n], (double)off[n] / n, (long long)maxdeg, n_orphans, extra.size(), (long long)c.nav);
+  }
+  return ix.set_graph(n, off.data(), nbr.data(), c.nav);
+}
+
 
 // SyncPrune's sort + SelectEdge (nsg.cpp:557-567, 655-685) for caller-supplied candidate lists: node nodes[i] with
 // candidates cands[i][0..cands_per_node) (-1 = none; the node itself is skipped) -> its <= out_degree pruned out-edges.
@@ -925,7 +869,7 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
   pa.out_ids = d_oi.as<u32>();
   pa.out_dist = d_od.as<float>();
   pa.out_deg = d_deg.as<u32>();
-  const bool vec4 = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(ix.d_rows_) & 15) == 0);
+  const bool vec4 = rows_vec4(ix.d_rows_, dim);
   const size_t shm = prune_lds_bytes(dim, R);
   if (vec4)
     hipLaunchKernelGGL((prune_kernel<true>), dim3((unsigned)m), dim3(256), shm, s, pa);
@@ -936,10 +880,7 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
   HIPCHK(hipMemcpyAsync(h_oi.data(), d_oi.p, (size_t)m * R * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(h_deg.data(), d_deg.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  for (int64_t i = 0; i < m; ++i) {
-    out_deg[i] = (int32_t)h_deg[i];
-    for (int j = 0; j < R; ++j) out_ids[i * R + j] = (u32)j < h_deg[i] ? (int64_t)h_oi[(size_t)i * R + j] : -1;
-  }
+  lists_to_abi(h_oi.data(), h_deg.data(), m, R, out_ids, out_deg);
   return EPS_OK;
 }
 
@@ -990,10 +931,7 @@ int32_t inter_insert(Index& ix, const int64_t* ids, const int32_t* deg, int64_t 
   HIPCHK(hipMemcpyAsync(r_ids.data(), o_ids.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(r_deg.data(), o_deg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  for (int64_t v = 0; v < n; ++v) {
-    out_deg[v] = (int32_t)r_deg[v];
-    for (int j = 0; j < R; ++j) out_ids[v * R + j] = (u32)j < r_deg[v] ? (int64_t)r_ids[(size_t)v * R + j] : -1;
-  }
+  lists_to_abi(r_ids.data(), r_deg.data(), n, R, out_ids, out_deg);
   return EPS_OK;
 }
 

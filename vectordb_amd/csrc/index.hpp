@@ -300,7 +300,7 @@ class Index : public IndexBase {
   friend void quant8_queries(Index&, const Quant8View&, const float*, int64_t, signed char*, float*);
   friend int32_t flat_mfma_search(Index&, const float*, int64_t, int, u64*, bool, int);
   friend int32_t flat_mfma_search_slice(Index&, const float*, int64_t, int, u64*, bool, int, int, bool);
-  friend int32_t graph_build(Index&, int64_t, const eps_build_params&, const BuildStage*);
+  friend struct BuildCtx;   // the stages of graph_build (graph_build.hip)
   friend int32_t select_edges(Index&, const int64_t*, int64_t, const int64_t*, int32_t, int32_t, int32_t, int64_t*, int32_t*);
   friend int32_t inter_insert(Index&, const int64_t*, const int32_t*, int64_t, int32_t, int64_t*, int32_t*);
   friend int32_t graph_search(Index&, const float*, int64_t, int, const eps_search_params&, u64*, int64_t*, int);

@@ -10,6 +10,9 @@
 
 namespace eps {
 
+// rows of `dim` floats starting at `rows` can be read in 16-byte pieces (the VEC4 form of the kernels that gather rows)
+inline bool rows_vec4(const float* rows, int64_t dim) { return (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(rows) & 15) == 0); }
+
 // ---------------------------------------------------------------- flat scan (BruteForceSearch, :717-768)
 struct FlatScanArgs {
   const float* rows;

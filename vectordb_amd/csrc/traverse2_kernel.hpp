@@ -24,6 +24,7 @@
 //     is_visited.clear()/resize(n), :711-714, is O(N) per query; here it is O(evaluations)).  If the log
 //     overflows the slot's bitmap is cleared wholesale by the workgroup.
 #pragma once
+#include "graph_host.hpp"
 #include "kernels.hpp"
 
 namespace eps {
@@ -87,14 +88,7 @@ constexpr int TRV2_UPF = 3;   // prefilter form of the kernel: fp32 rows in flig
 constexpr int TRV2_NL = 3;    // ... and 16-byte pieces of each (row_dists, device_common.hpp).  r5: 3 x 3 (4 x 1 until r4; profiles/r5_traverse_lab_10M_proxy.txt)
 constexpr int TRV2_U8 = 3;    // prefilter: mirror rows in flight per lane group (2 until r4) ...
 constexpr int TRV2_NL8 = 3;   // ... and 16-byte pieces of each per lane
-constexpr int TRV2_SB = 4096;       // keys of the LDS staging block of the QGLOBAL bitonic sort
-constexpr int TRV2_MAXT = 128;      // the reference's limit for IntraQueryThreads (config/config.hpp:29)
-// ints of scalar scratch: 16 scalars, nine [TS] per-worker arrays, [16] per-wave counts, [TS + 16] edge offsets; TS = T rounded up to 16
-__host__ __device__ inline int trv2_tstride(int T) { return T <= 16 ? 16 : (T + 15) & ~15; }
-__host__ __device__ inline int trv2_sh_ints(int T) { return 48 + 10 * trv2_tstride(T); }
-// bytes of the prefilter's LDS block: the query's four statistics, the query on the 8-bit grid, alignment spare
-__host__ __device__ inline int trv2_q8len(int dim) { return (dim + 15) & ~15; }
-__host__ __device__ inline int trv2_pf_bytes(int dim) { return 16 + 16 + trv2_q8len(dim); }
+// TRV2_SB, TRV2_MAXT and the sizes of the LDS arrays below (trv2_*, traverse2_hash_slots, traverse2_lds_bytes): graph_host.hpp
 constexpr u32 TRV2_NONE = 0xFFFFFFFFu;
 
 __device__ __forceinline__ u64 q2key(float d, u32 id) { return ((u64)f2ord(d + 0.0f) << 32) | ((u64)id << 1); }
@@ -832,20 +826,6 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
     atomicAdd(&a.counters[3], rounds);
     atomicAdd(&a.counters[4], fetched);
   }
-}
-
-// LDS bytes of one workgroup; qglobal = queues in HBM
-inline int traverse2_hash_slots(int T, int dp) {
-  if (T <= 1) return 0;
-  int h = 64;
-  while (h < 2 * T * dp) h <<= 1;
-  return h;
-}
-inline size_t traverse2_lds_bytes(int dim, int T, int Lq, int64_t qtot, int dp, bool qglobal, bool prefilter = false, int cols8 = 0) {
-  const int qstride = (dim + 3) & ~3;
-  const size_t ecap = (size_t)T * dp;
-  return (size_t)qstride * 4 + (qglobal ? (size_t)TRV2_SB : (size_t)qtot) * 8 + ecap * (8 + 8 + 4 + 4 + 4 + 4) + (size_t)traverse2_hash_slots(T, dp) * 8 +
-         ((qglobal || T == 1) ? 0 : (size_t)2 * Lq * 4) + (size_t)trv2_sh_ints(T) * 4 + (prefilter ? (size_t)trv2_pf_bytes(cols8 > dim ? cols8 : dim) : 0);
 }
 
 }  // namespace eps
