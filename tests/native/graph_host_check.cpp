@@ -1,5 +1,5 @@
 // Stand-alone host check of csrc/graph_host.hpp - the seed list of a search, the connectivity repair and CSR assembly of the build, the launch plan
-// of the traversal with its refusals, the tail merge's arithmetic - for a CPU build under -fsanitize=address,undefined
+// of the traversal with its refusals, the tail merge's arithmetic, the LDS bytes of the build's launches and their refusal - for a CPU build under -fsanitize=address,undefined
 // (tests/test_graph_host_cpu.py builds and runs it).  Every list lives in a heap block exactly as long as the library's, so an index beyond a
 // list is a heap overflow the sanitizer reports.
 //   graph_host_check                    all checks; prints "graph_host_check OK"
@@ -359,6 +359,43 @@ static void tails() {
   CHECK(r.msg == "search: limit > 8192 with an un-indexed tail is not supported (rebuild the graph over the new rows)");
 }
 
+// ------------------------------------------------------------------------------------------------ LDS of the build's launches
+static void build_lds() {
+  const size_t KB = 1024, dev = 160 * KB;   // a gfx950 workgroup's LDS
+  // SelectEdge at out_degree 50: 20 bytes per (padded) dimension, the pool, kept lists, scalars
+  CHECK(prune_lds_bytes(768, 50) == 48800 && prune_lds_bytes(4096, 50) == 115360 && prune_lds_bytes(6520, 50) == 163840 && prune_lds_bytes(8192, 50) == 197280);
+  CHECK(prune_lds_bytes(765, 50) == prune_lds_bytes(768, 50) && prune_lds_bytes(769, 50) == prune_lds_bytes(772, 50));
+  CHECK(prune_lds_bytes(768, 512) == 48800 + 8 * 462);
+  // Link's search: 4 bytes per dimension, queue, chunk buffers, scalars; + the LDS visited hash, + the prefilter's block
+  CHECK(traverse_lds_bytes(768, 512, false) == 3072 + 4096 + 4096 + 1024 + 256);
+  CHECK(traverse_lds_bytes(768, 512, true) == traverse_lds_bytes(768, 512, false) + 32768);
+  CHECK(traverse_lds_bytes(768, 2048, false, true, 768) == 3072 + 16384 + 4096 + 1024 + 256 + 32 + 768);
+  CHECK(traverse_lds_bytes(770, 512, false, true, 1024) == 3088 + 4096 + 4096 + 1024 + 256 + 32 + 1024);
+  CHECK(traverse_lds_bytes(8192, 2048, true, true, 8192) == 32768 + 16384 + 4096 + 1024 + 256 + 32768 + 32 + 8192);   // (95 KB: SelectEdge is the larger at every width)
+  for (int dim : {1, 768, 4096, 6520, 8192})
+    for (int R : {1, 50, 512})
+      CHECK(build_lds_need(dim, R, 2048, true, true, dim) == std::max(prune_lds_bytes(dim, R), traverse_lds_bytes(dim, 2048, true, true, dim)));
+  // the check: what fits passes untouched, what does not is refused with the width that would
+  for (int dim : {768, 4096, 6520}) {
+    Refusal r;
+    CHECK(build_lds_check(dim, 50, 512, false, false, 0, dev, &r) == EPS_OK && r.code == EPS_OK && r.msg.empty());
+  }
+  for (int dim : {6521, 6524, 8192}) {
+    Refusal r;
+    CHECK(build_lds_check(dim, 50, 512, false, false, 0, dev, &r) == EPS_DB_UNSUPPORTED_ERROR && r.code == EPS_DB_UNSUPPORTED_ERROR && r.err_class == EPS_ERRCLASS_DEVICE_RANGE);
+    CHECK(r.msg.find("width limit of the graph build at out_degree 50: 6520 dimensions") != std::string::npos);
+    CHECK(r.msg.find("rows of " + std::to_string(dim) + " dimensions need " + std::to_string(prune_lds_bytes(dim, 50)) + " bytes of LDS per workgroup, the device has 163840") != std::string::npos);
+  }
+  {   // out_degree moves the limit; a device with 64 KB has its own
+    Refusal r;
+    CHECK(build_lds_check(6520, 512, 512, false, false, 0, dev, &r) == EPS_DB_UNSUPPORTED_ERROR && r.msg.find("out_degree 512: 6332 dimensions") != std::string::npos);
+    Refusal r2;
+    CHECK(build_lds_check(2048, 50, 512, false, false, 0, 64 * KB, &r2) == EPS_DB_UNSUPPORTED_ERROR && r2.msg.find(": 1604 dimensions") != std::string::npos);
+    Refusal r3;
+    CHECK(build_lds_check(1604, 50, 512, false, false, 0, 64 * KB, &r3) == EPS_OK);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ seeds of a graph in a file
 static int seeds_of_file(const char* path, int64_t L) {
   FILE* f = fopen(path, "rb");
@@ -386,6 +423,7 @@ int main(int argc, char** argv) {
   refusals();
   pinned();
   tails();
+  build_lds();
   if (failures) {
     printf("graph_host_check: %d check(s) failed\n", failures);
     return 1;

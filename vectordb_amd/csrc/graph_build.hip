@@ -31,7 +31,7 @@
 
 namespace eps {
 
-constexpr int PRUNE_POOL = 4096;   // sorted candidate pool per node (LDS)
+// (PRUNE_POOL, the sorted candidate pool per node in LDS, and the LDS bytes of the launches: graph_host.hpp)
 constexpr int GHASH_SLOTS = 32768; // visited hash slots per search of Link / connectivity in HBM (BuildCtx::link_stage)
 
 // ------------------------------------------------------------------------------------------------ kNN extraction
@@ -145,29 +145,58 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   for (int i = tid; i < PRUNE_POOL; i += 256) pool[i] = KEY_EMPTY;
   for (int i = tid; i < qstride; i += 256) sq[i] = i < dim ? a.rows[v * dim + i] : 0.f;
   __syncthreads();
-  // ---- gather the pool
-  if (a.log) {
-    const u32 cnt = a.log_cnt[blockIdx.x];
-    const u64* src = a.log + (int64_t)blockIdx.x * a.log_cap;
-    for (u32 i = tid; i < cnt; i += 256) {
-      const int slot = atomicAdd(&sh[0], 1);
-      if (slot < PRUNE_POOL) pool[slot] = src[i];
+  // ---- gather the pool: the keyed sources (search log, own edges, offers) as one flat list of `total` keys.  (The kNN list below comes
+  // on top of it: Link's log + list and select_edges' list alone stay below PRUNE_POOL by their callers' limits.)
+  const u32 nA = a.log ? a.log_cnt[blockIdx.x] : 0u;
+  const u32 nC = a.idsC ? (a.cntC[v] < (u32)a.capC ? a.cntC[v] : (u32)a.capC) : 0u;
+  const int64_t baseD = a.offD ? (int64_t)a.offD[v] : v * a.capD;
+  const u32 nD = a.idsD ? (a.offD ? (u32)(a.offD[v + 1] - a.offD[v]) : (a.cntD[v] < (u32)a.capD ? a.cntD[v] : (u32)a.capD)) : 0u;
+  const u32 total = nA + nC + nD;
+  auto src_key = [&](u32 i) -> u64 {
+    if (i < nA) return a.log[(int64_t)blockIdx.x * a.log_cap + i];
+    i -= nA;
+    if (i < nC) return make_key(a.distC[v * a.capC + i], a.idsC[v * a.capC + i]);
+    i -= nC;
+    return make_key(a.distD[baseD + i], a.idsD[baseD + i]);
+  };
+  if (total <= (u32)PRUNE_POOL) {
+    for (u32 i = tid; i < total; i += 256) pool[i] = src_key(i);
+    if (tid == 0) sh[0] = (int)total;
+  } else {
+    // More keys than the pool holds (a hub of InterInsert): the pool is the PRUNE_POOL SMALLEST keys by (dist, id), repeats counted - not
+    // the first arrivals.  T = the smallest key with |{key <= T}| >= PRUNE_POOL, found bit by bit; everything below T goes in, and copies of
+    // T fill what is left: equal keys are one (dist, id), so which copies they are changes nothing.
+    auto block_count = [&](int local) {
+      for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+      if (lane == 0) sh[8 + wave] = local;
+      __syncthreads();
+      const int c = sh[8] + sh[9] + sh[10] + sh[11];
+      __syncthreads();
+      return c;
+    };
+    u64 T = 0;
+    for (int bit = 63; bit >= 0; --bit) {
+      const u64 probe = T | ((1ull << bit) - 1ull);   // this bit 0, every lower bit 1
+      int local = 0;
+      for (u32 i = tid; i < total; i += 256) local += src_key(i) <= probe ? 1 : 0;
+      if (block_count(local) < PRUNE_POOL) T |= 1ull << bit;
     }
-  }
-  if (a.idsC) {
-    const u32 cnt = a.cntC[v] < (u32)a.capC ? a.cntC[v] : (u32)a.capC;
-    for (u32 i = tid; i < cnt; i += 256) {
-      const int slot = atomicAdd(&sh[0], 1);
-      if (slot < PRUNE_POOL) pool[slot] = make_key(a.distC[v * a.capC + i], a.idsC[v * a.capC + i]);
+    int local = 0;
+    for (u32 i = tid; i < total; i += 256) local += src_key(i) < T ? 1 : 0;
+    const int below = block_count(local);   // < PRUNE_POOL by the choice of T
+    if (tid == 0) sh[4] = 0;
+    __syncthreads();
+    for (u32 i = tid; i < total; i += 256) {
+      const u64 key = src_key(i);
+      if (key < T) {
+        pool[atomicAdd(&sh[0], 1)] = key;
+      } else if (key == T) {
+        const int e = below + atomicAdd(&sh[4], 1);
+        if (e < PRUNE_POOL) pool[e] = key;
+      }
     }
-  }
-  if (a.idsD) {
-    const int64_t baseD = a.offD ? (int64_t)a.offD[v] : v * a.capD;
-    const u32 cnt = a.offD ? (u32)(a.offD[v + 1] - a.offD[v]) : (a.cntD[v] < (u32)a.capD ? a.cntD[v] : (u32)a.capD);
-    for (u32 i = tid; i < cnt; i += 256) {
-      const int slot = atomicAdd(&sh[0], 1);
-      if (slot < PRUNE_POOL) pool[slot] = make_key(a.distD[baseD + i], a.idsD[baseD + i]);
-    }
+    __syncthreads();
+    if (tid == 0) sh[0] = PRUNE_POOL;
   }
   __syncthreads();
   if (a.listB) {  // "avoid lose nearest neighbor in knng" (nsg.cpp:542-557): distances to the kNN list of v
@@ -223,7 +252,7 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   if (tid == 0) {
     sh[1] = 0;  // nk
     sh[2] = 0;  // cursor
-    sh[3] = 0;  // scanned
+    sh[3] = 0;  // pool positions passed (repeats not counted)
   }
   __syncthreads();
   const bool unlimited = a.depth <= 0;
@@ -252,16 +281,20 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
     if (tid == 0) {   // the next <= PB unique candidates
       int c = sh[2];
       int nb = 0;
-      while (nb < PB && c < P2 && (unlimited || sh[3] < a.depth)) {
+      // depth: the reference scans the positions 0 .. depth of its sorted pool (nsg.cpp:655-685: `cursor < depth && ++cursor < size`), the
+      // node's own position included when it is there - depth candidates then, depth + 1 when the node is not in its pool.  sh[3] counts
+      // the positions of the pool without repeats that were passed.
+      while (nb < PB && c < P2 && (unlimited || sh[3] <= a.depth)) {
         const u64 key = pool[c];
         if (key == KEY_EMPTY) break;
-        const bool dup = (c > 0 && pool[c - 1] == key) || key_id(key) == (u32)v;
-        if (!dup) {
-          sh[16 + nb] = c;
-          sh[24 + nb] = 0;
-          for (int b2 = 0; b2 < PB; ++b2) sh[32 + nb * PB + b2] = 0;
-          ++nb;
+        if (!(c > 0 && pool[c - 1] == key)) {
           sh[3] += 1;
+          if (key_id(key) != (u32)v) {
+            sh[16 + nb] = c;
+            sh[24 + nb] = 0;
+            for (int b2 = 0; b2 < PB; ++b2) sh[32 + nb * PB + b2] = 0;
+            ++nb;
+          }
         }
         ++c;
       }
@@ -366,8 +399,34 @@ __global__ void rev_fill_kernel(const u32* ids, const float* dist, const u32* de
     if (e__ != hipSuccess) return ix.hip_fail(e__, #expr);   \
   } while (0)
 
-static size_t prune_lds_bytes(int dim, int R) {   // v's vector, pool, kept ids + distances, 64 scalars, 4 staged candidate vectors
-  return (size_t)((dim + 3) & ~3) * 4 + (size_t)PRUNE_POOL * 8 + (size_t)R * 8 + 64 * 4 + 16 + (size_t)4 * ((dim + 3) & ~3) * 4;
+// LDS bytes a workgroup of this device can have: the launches of the build are compared against it before anything is launched.  The
+// per-workgroup attribute decides (163 840 on gfx950, the same as its CU's); the CU's figure stands in only where that one reads nothing -
+// on a device whose workgroups get less than their CU's LDS the larger figure would pass a launch that cannot be made
+static size_t device_lds_limit(int device) {
+  int per_block = 0, per_cu = 0;
+  if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) per_block = 0;
+  if (per_block <= 0 && hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess) per_cu = 0;
+  (void)hipGetLastError();
+  const int m = per_block > 0 ? per_block : per_cu;
+  return m > 0 ? (size_t)m : (size_t)64 * 1024;
+}
+
+// prune_kernel with `shm` bytes of dynamic LDS.  The attribute is set as traverse.hip's launch_trv2 sets it (idempotent and cheap): launches of 74 400
+// and 115 360 bytes went through without it on the runtime this was measured with, but that is the runtime's default, not a promise
+static void launch_prune(bool vec4, unsigned blocks, size_t shm, hipStream_t s, const PruneArgs& pa) {
+  if (vec4) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prune_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    hipLaunchKernelGGL((prune_kernel<true>), dim3(blocks), dim3(256), shm, s, pa);
+  } else {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prune_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    hipLaunchKernelGGL((prune_kernel<false>), dim3(blocks), dim3(256), shm, s, pa);
+  }
+}
+// refuses a SelectEdge launch the device has no LDS for (select_edges, inter_insert, the build)
+static int32_t prune_lds_refusal(Index& ix, int dim, int R) {
+  Refusal r;
+  if (build_lds_check(dim, R, 0, false, false, 0, device_lds_limit(ix.device_), &r) != EPS_OK) return ix.fail(r.code, r.msg, r.err_class);
+  return EPS_OK;
 }
 
 // InterInsert (nsg.cpp:583-653), batched: every edge v->u offers v (with dist(v,u)) to u; every node then runs SelectEdge(limit =
@@ -379,6 +438,7 @@ static int32_t inter_insert_device(Index& ix, const u32* nsg_ids, const float* n
   const int dim = (int)ix.dim_;
   const bool vec4 = rows_vec4(ix.d_rows_, dim);
   const size_t prn_shm = prune_lds_bytes(dim, R);
+  if (const int32_t rc = prune_lds_refusal(ix, dim, R)) return rc;
   DevBuf rev_ids, rev_dist, rev_cnt, rev_off;
   if (!rev_cnt.reserve((size_t)n * 4) || !rev_off.reserve((size_t)(n + 1) * 8) || !out_ids.reserve((size_t)n * R * 4) ||
       !out_dist.reserve((size_t)n * R * 4) || !out_deg.reserve((size_t)n * 4))
@@ -418,10 +478,7 @@ static int32_t inter_insert_device(Index& ix, const u32* nsg_ids, const float* n
   for (int64_t v0 = 0; v0 < n; v0 += 1 << 20) {
     const int64_t nb = std::min<int64_t>(1 << 20, n - v0);
     pa.v0 = v0;
-    if (vec4)
-      hipLaunchKernelGGL((prune_kernel<true>), dim3((unsigned)nb), dim3(256), prn_shm, s, pa);
-    else
-      hipLaunchKernelGGL((prune_kernel<false>), dim3((unsigned)nb), dim3(256), prn_shm, s, pa);
+    launch_prune(vec4, (unsigned)nb, prn_shm, s, pa);
   }
   HIPCHK(hipGetLastError());
   return EPS_OK;
@@ -579,15 +636,21 @@ int32_t BuildCtx::navigation_stage() {
   return EPS_OK;
 }
 
+template <bool VEC4, bool HASHVIS>
+static void launch_trv(unsigned blocks, size_t shm, hipStream_t s, const TraverseArgs& ta) {   // (the attribute: see launch_prune)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(traverse_kernel<VEC4, HASHVIS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  hipLaunchKernelGGL((traverse_kernel<VEC4, HASHVIS>), dim3(blocks), dim3(256), shm, s, ta);
+}
+
 // one search per block of ta's launch, over the visited set the build runs with (link_stage)
 hipError_t BuildCtx::launch_link_search(int64_t nb) {
   if (bitmap_vis) {   // exact visited set: one n-bit bitmap per search of the batch, zeroed per batch
     hipError_t e = hipMemsetAsync(visb.p, 0, (size_t)nb * vis_words * 4, s);
     if (e != hipSuccess) return e;
     if (vec4)
-      hipLaunchKernelGGL((traverse_kernel<true, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+      launch_trv<true, false>((unsigned)nb, trv_shm_bm, s, ta);
     else
-      hipLaunchKernelGGL((traverse_kernel<false, false>), dim3((unsigned)nb), dim3(256), trv_shm_bm, s, ta);
+      launch_trv<false, false>((unsigned)nb, trv_shm_bm, s, ta);
   } else {
     const size_t shm = ghash_vis ? trv_shm_bm : trv_shm;   // (the LDS layout without the table)
     if (ghash_vis) {
@@ -595,9 +658,9 @@ hipError_t BuildCtx::launch_link_search(int64_t nb) {
       if (e != hipSuccess) return e;
     }
     if (vec4)
-      hipLaunchKernelGGL((traverse_kernel<true, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
+      launch_trv<true, true>((unsigned)nb, shm, s, ta);
     else
-      hipLaunchKernelGGL((traverse_kernel<false, true>), dim3((unsigned)nb), dim3(256), shm, s, ta);
+      launch_trv<false, true>((unsigned)nb, shm, s, ta);
   }
   return hipSuccess;
 }
@@ -640,9 +703,13 @@ int32_t BuildCtx::link_stage() {
   if (Lp2 < Ls) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, "build: search_length > 2048 is not supported");
   Lcap = Lp2;
   // 8-bit lower-bound prefilter of the searches' distance step (traverse_kernel.hpp, step 3a): the mirror is the one the kNN stage
-  // just scanned; EPS_BUILD_PREFILTER=0 turns it off (A/B - the graph is the same either way)
+  // just scanned; EPS_BUILD_PREFILTER=0 turns it off (A/B - the graph is the same either way).  Only where the field's metric is L2: the
+  // mirror's start values, the prepared queries and the key unit are those of the FIELD's metric, and these searches are L2 whatever the
+  // field's - under COSINE / DOT_PRODUCT the test dropped rows inside the bound (half the Link lists of a 3000 x 16 tie table came out short).
+  // Such fields' searches read the fp32 rows; what that costs their Link has not been measured
   prefilter = dim >= 128;
   if (const char* e = tune_env("EPS_BUILD_PREFILTER")) prefilter = atoi(e) != 0;
+  if (ix.metric_ != 0) prefilter = false;
   if (prefilter) {
     const int32_t rc = quant8_view(ix, &q8v);
     if (rc != EPS_OK) q8v = Quant8View();   // (optional: without the mirror the searches read the fp32 rows, the graph is the same)
@@ -650,6 +717,10 @@ int32_t BuildCtx::link_stage() {
   }
   trv_shm = traverse_lds_bytes(dim, Lp2, true, prefilter, q8v.cols8);
   trv_shm_bm = traverse_lds_bytes(dim, Lp2, false, prefilter, q8v.cols8);
+  {   // (graph_build checked the width before the kNN stage, without the prefilter's block: this is the exact figure)
+    Refusal r;
+    if (build_lds_check(dim, R, Lp2, !bitmap_vis && !ghash_vis, prefilter, q8v.cols8, device_lds_limit(ix.device_), &r) != EPS_OK) return ix.fail(r.code, r.msg, r.err_class);
+  }
   const size_t prn_shm = prune_lds_bytes(dim, R);
   ta.rows = ix.d_rows_;
   ta.dim = dim;
@@ -719,10 +790,7 @@ int32_t BuildCtx::link_stage() {
       }
     }
     pa.v0 = v0;
-    if (vec4)
-      hipLaunchKernelGGL((prune_kernel<true>), dim3((unsigned)nb), dim3(256), prn_shm, s, pa);
-    else
-      hipLaunchKernelGGL((prune_kernel<false>), dim3((unsigned)nb), dim3(256), prn_shm, s, pa);
+    launch_prune(vec4, (unsigned)nb, prn_shm, s, pa);
   }
   HIPCHK(hipGetLastError());
   lap("Link (search + SelectEdge)");
@@ -804,6 +872,10 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   if (c.K <= 0 || c.R <= 0 || c.Ls <= 0 || c.K + 1 > 1024 || c.R > 512)
     return ix.fail(EPS_USER_ERROR, "build: unsupported parameters (need 0 < knng < 1024, 0 < out_degree <= 512)");
   int32_t rc;
+  {   // the width limit, before the most expensive stage runs: Link's search with the smallest queue it can get, SelectEdge at R
+    Refusal r;
+    if (build_lds_check(c.dim, c.R, 512, false, false, 0, device_lds_limit(ix.device_), &r) != EPS_OK) return ix.fail(r.code, r.msg, r.err_class);
+  }
   if ((rc = c.start_timer()) != EPS_OK) return rc;
   if ((rc = c.knn_stage()) != EPS_OK) return rc;
   if (hook && hook->stop_after == 1) return c.export_knn();
@@ -841,6 +913,7 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
     return ix.fail(EPS_USER_ERROR, "select_edges: bad arguments");
   hipStream_t s = ix.stream_;
   const int dim = (int)ix.dim_;
+  if (const int32_t rc = prune_lds_refusal(ix, dim, R)) return rc;
   std::vector<u32> h_nodes((size_t)m), h_c((size_t)m * cpn);
   for (int64_t i = 0; i < m; ++i) {
     if (nodes[i] < 0 || nodes[i] >= ix.n_rows_) return ix.fail(EPS_USER_ERROR, "select_edges: node out of range");
@@ -871,10 +944,7 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
   pa.out_deg = d_deg.as<u32>();
   const bool vec4 = rows_vec4(ix.d_rows_, dim);
   const size_t shm = prune_lds_bytes(dim, R);
-  if (vec4)
-    hipLaunchKernelGGL((prune_kernel<true>), dim3((unsigned)m), dim3(256), shm, s, pa);
-  else
-    hipLaunchKernelGGL((prune_kernel<false>), dim3((unsigned)m), dim3(256), shm, s, pa);
+  launch_prune(vec4, (unsigned)m, shm, s, pa);
   HIPCHK(hipGetLastError());
   std::vector<u32> h_oi((size_t)m * R), h_deg((size_t)m);
   HIPCHK(hipMemcpyAsync(h_oi.data(), d_oi.p, (size_t)m * R * 4, hipMemcpyDeviceToHost, s));
@@ -907,6 +977,7 @@ __global__ __launch_bounds__(256) void edge_dist_kernel(const float* rows, int d
 int32_t inter_insert(Index& ix, const int64_t* ids, const int32_t* deg, int64_t n, int32_t R, int64_t* out_ids, int32_t* out_deg) {
   if (n <= 0) return EPS_OK;
   if (!ids || !deg || !out_ids || !out_deg || R <= 0 || R > 512 || n != ix.n_rows_) return ix.fail(EPS_USER_ERROR, "inter_insert: bad arguments");
+  if (const int32_t rc = prune_lds_refusal(ix, (int)ix.dim_, R)) return rc;
   hipStream_t s = ix.stream_;
   std::vector<u32> h_ids((size_t)n * R, TRV_NONE), h_deg((size_t)n);
   for (int64_t v = 0; v < n; ++v) {

@@ -135,6 +135,47 @@ inline void lists_to_abi(const uint32_t* ids, const uint32_t* deg, int64_t rows,
   }
 }
 
+// ------------------------------------------------------------------------------------------------ LDS layout of the build's kernels
+constexpr int PRUNE_POOL = 4096;   // sorted candidate pool per node of prune_kernel (LDS)
+constexpr int TRV_HASH = 8192;     // LDS visited hash slots of traverse_kernel (HASHVIS mode), power of two
+constexpr int TRV_CHUNK = 256;     // neighbours traverse_kernel handles per sub-round
+constexpr int BUILD_MAX_DIM = 8192;   // widest row the library accepts
+
+// prune_kernel: v's vector, pool, kept ids + distances, 64 scalars, 4 staged candidate vectors
+EPS_GRAPH_HD inline size_t prune_lds_bytes(int dim, int R) {
+  return (size_t)((dim + 3) & ~3) * 4 + (size_t)PRUNE_POOL * 8 + (size_t)R * 8 + 64 * 4 + 16 + (size_t)4 * ((dim + 3) & ~3) * 4;
+}
+// traverse_kernel: the query, the queue, two chunks of keys, a chunk of ids, 64 scalars, the visited hash (LDS form), the prefilter's block
+EPS_GRAPH_HD inline size_t traverse_lds_bytes(int dim, int Lp2, bool hashvis, bool prefilter = false, int cols8 = 0) {
+  const int qstride = (dim + 3) & ~3;
+  return (size_t)qstride * 4 + (size_t)Lp2 * 8 + TRV_CHUNK * 8 * 2 + TRV_CHUNK * 4 + 64 * 4 + (hashvis ? TRV_HASH * 4 : 0) +
+         (prefilter ? (size_t)(16 + 16 + (((cols8 > dim ? cols8 : dim) + 15) & ~15)) : 0);
+}
+
+struct Refusal {   // what IndexBase::fail takes
+  int32_t code = EPS_OK, err_class = 0;
+  std::string msg;
+};
+
+// What a build's two LDS-hungry kernels need against what a workgroup of the device can have (lds_limit bytes), BEFORE anything is launched:
+// a launch above the limit fails inside the runtime, and the caller would read a HIP error string.  need = the larger of the Link search
+// (queue of Lp2 keys, visited hash in LDS when hashvis) and SelectEdge at out-degree R.  The refusal names the widest row the same build
+// would still run with, found by arithmetic on the two layouts.
+inline size_t build_lds_need(int dim, int R, int Lp2, bool hashvis, bool prefilter, int cols8) {
+  return std::max(prune_lds_bytes(dim, R), traverse_lds_bytes(dim, Lp2, hashvis, prefilter, cols8));
+}
+inline int32_t build_lds_check(int dim, int R, int Lp2, bool hashvis, bool prefilter, int cols8, size_t lds_limit, Refusal* r) {
+  const size_t need = build_lds_need(dim, R, Lp2, hashvis, prefilter, cols8);
+  if (need <= lds_limit) return EPS_OK;
+  int widest = 0;   // largest multiple of 4 that fits (the mirror row of another width is not known here: the width itself stands in)
+  for (int w = 4; w <= BUILD_MAX_DIM; w += 4)
+    if (build_lds_need(w, R, Lp2, hashvis, prefilter, 0) <= lds_limit) widest = w;
+  r->msg = "build: rows of " + std::to_string(dim) + " dimensions need " + std::to_string(need) + " bytes of LDS per workgroup, the device has " +
+           std::to_string(lds_limit) + " (width limit of the graph build at out_degree " + std::to_string(R) + ": " + std::to_string(widest) + " dimensions)";
+  r->err_class = EPS_ERRCLASS_DEVICE_RANGE;
+  return r->code = EPS_DB_UNSUPPORTED_ERROR;
+}
+
 // ------------------------------------------------------------------------------------------------ LDS layout of traverse2_kernel
 constexpr int TRV2_SB = 4096;       // keys of the LDS staging block of the QGLOBAL bitonic sort
 constexpr int TRV2_MAXT = 128;      // the reference's limit for IntraQueryThreads (config/config.hpp:29)
@@ -160,11 +201,6 @@ EPS_GRAPH_HD inline size_t traverse2_lds_bytes(int dim, int T, int Lq, int64_t q
 }
 
 // ------------------------------------------------------------------------------------------------ launch plan of a traversal
-struct Refusal {   // what IndexBase::fail takes
-  int32_t code = EPS_OK, err_class = 0;
-  std::string msg;
-};
-
 struct TrvIn {
   int64_t n_indexed, nq;
   int dim;

@@ -2,6 +2,7 @@
 // search of the Link step on the kNN graph, which logs the L closest nodes it evaluated for SyncPrune.  (The search path's
 // traversal is traverse2_kernel.hpp.)
 #pragma once
+#include "graph_host.hpp"
 #include "kernels.hpp"
 
 namespace eps {
@@ -40,10 +41,9 @@ struct TraverseArgs {
   float u8, slack8;
 };
 
-constexpr int TRV_HASH = 8192;   // LDS visited hash slots (HASHVIS mode), power of two
+// (TRV_HASH, TRV_CHUNK and the LDS bytes of a launch, traverse_lds_bytes: graph_host.hpp)
 constexpr u32 TRV_NONE = 0xFFFFFFFFu;
 
-constexpr int TRV_CHUNK = 256;   // neighbours handled per sub-round
 constexpr int TRV_MAXM = 16;
 
 // queue key: ord(dist) << 32 | id << 1 | checked
@@ -424,13 +424,6 @@ __global__ __launch_bounds__(256) void traverse_kernel(TraverseArgs a) {
     if (pf && a.counters_n > 3) atomicAdd(&a.counters[3], (unsigned long long)sh[43]);   // fp32 rows step 3 still read
     if (HASHVIS && a.counters_n > 2 && sh[6] + TRV_CHUNK > hlimit) atomicAdd(&a.counters[2], 1ull);   // searches that filled the visited hash
   }
-}
-
-
-inline size_t traverse_lds_bytes(int dim, int Lp2, bool hashvis, bool prefilter = false, int cols8 = 0) {
-  const int qstride = (dim + 3) & ~3;
-  return (size_t)qstride * 4 + (size_t)Lp2 * 8 + TRV_CHUNK * 8 * 2 + TRV_CHUNK * 4 + 64 * 4 + (hashvis ? TRV_HASH * 4 : 0) +
-         (prefilter ? (size_t)(16 + 16 + (((cols8 > dim ? cols8 : dim) + 15) & ~15)) : 0);
 }
 
 }  // namespace eps
