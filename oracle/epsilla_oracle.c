@@ -321,6 +321,32 @@ typedef struct {
   int64_t evals;
 } eo_ctx;
 
+/* Optional evaluation log (test infrastructure for the device's filter_in_traversal rule): while set, every `++evals` site of
+ * eo_search_impl - the seed loop and expand_one - appends (id, fp32 distance, beyond) in evaluation order; beyond = 1 where the
+ * `dist > *bound` test dropped the row when it was evaluated (seeds: 0).  At most `cap` entries are stored; eo_eval_log_count()
+ * is the number appended since the last eo_set_eval_log, stored or not.  eo_set_eval_log(NULL, NULL, NULL, 0) switches it off.
+ * The log reads what the walk computes and writes nothing the walk reads. */
+static int64_t* g_elog_ids = NULL;
+static float* g_elog_dist = NULL;
+static uint8_t* g_elog_beyond = NULL;
+static int64_t g_elog_cap = 0, g_elog_n = 0;
+void eo_set_eval_log(int64_t* ids, float* dist, uint8_t* beyond, int64_t cap) {
+  g_elog_ids = ids;
+  g_elog_dist = dist;
+  g_elog_beyond = beyond;
+  g_elog_cap = (ids && dist && beyond) ? cap : 0;
+  g_elog_n = 0;
+}
+int64_t eo_eval_log_count(void) { return g_elog_n; }
+static void elog_append(int64_t id, float dist, int beyond) {
+  if (g_elog_n < g_elog_cap) {
+    g_elog_ids[g_elog_n] = id;
+    g_elog_dist[g_elog_n] = dist;
+    g_elog_beyond[g_elog_n] = (uint8_t)beyond;
+  }
+  if (g_elog_cap) ++g_elog_n;
+}
+
 /* a7  ExpandOneCandidate (:384-444).  `bound` points at the live worst-of-master slot (:546). */
 static int64_t expand_one(eo_ctx* c, int64_t cand_id, const float* bound, eo_cand* queue, int64_t* qsize, int64_t cap) {
   int64_t nk = cap;
@@ -330,6 +356,7 @@ static int64_t expand_one(eo_ctx* c, int64_t cand_id, const float* bound, eo_can
     c->visited[nb] = 1;
     ++c->evals;
     float dist = eo_dist(c->metric, c->rows + nb * c->d, c->q, c->d);
+    elog_append(nb, dist, dist > *bound);
     if (dist > *bound) continue;
     eo_cand cand = {nb, dist, 0};
     int64_t r = add_into_queue(queue, qsize, cap, &cand);
@@ -370,6 +397,7 @@ int64_t eo_search_impl(int metric, const float* rows, int64_t d, int64_t n, cons
     master[i].id = v;
     master[i].dist = eo_dist(metric, rows + v * d, q, d);
     master[i].checked = 0;
+    elog_append(v, master[i].dist, 0);
   }
   qsort(master, (size_t)L, sizeof(eo_cand), cand_cmp_qsort);
   sizes[T - 1] = L;

@@ -97,6 +97,10 @@ class Oracle:
         L.eo_search_impl.restype = i64
         L.eo_search_impl.argtypes = [C.c_int, fptr, i64, i64, iptr, iptr, iptr, fptr, C.c_int, i64, i64, i64,
                                      C.POINTER(EoCand), u8ptr]
+        L.eo_set_eval_log.restype = None
+        L.eo_set_eval_log.argtypes = [iptr, fptr, u8ptr, i64]
+        L.eo_eval_log_count.restype = i64
+        L.eo_eval_log_count.argtypes = []
         L.eo_set_schedule.restype = C.c_int
         L.eo_set_schedule.argtypes = [C.c_int]
         L.eo_search.restype = i64
@@ -166,19 +170,32 @@ class Oracle:
         self.L.eo_prepare_init_ids(n, _i(off), _i(nbr), nav, L, _i(out))
         return out
 
-    def search_impl(self, metric, rows, off, nbr, init_ids, q, T=1, L=500, Lq=None, I=15, lockstep=False):
-        """lockstep=True: the T > 1 interleaving the device kernel implements (see eo_search_impl)."""
+    def search_impl(self, metric, rows, off, nbr, init_ids, q, T=1, L=500, Lq=None, I=15, lockstep=False, log=False):
+        """lockstep=True: the T > 1 interleaving the device kernel implements (see eo_search_impl).
+        log=True: additionally the evaluation log (eo_set_eval_log) - ids int64, fp32 distances, `beyond` flags uint8, one entry per
+        distance evaluation in evaluation order (a walk evaluates a row at most once: at most n entries)."""
         Lq = L if Lq is None else Lq
         self.L.eo_set_schedule(int(lockstep))
         rows = np.ascontiguousarray(rows, np.float32)
         n = len(off) - 1
         set_l = (EoCand * ((T - 1) * Lq + L))()
         visited = np.zeros(n, np.uint8)
-        ev = self.L.eo_search_impl(metric, _f(rows), rows.shape[1], n, _i(off), _i(nbr), _i(init_ids), _f(q), T, L, Lq,
-                                   I, set_l, visited.ctypes.data_as(u8ptr))
+        if log:
+            lid, ld, lb = np.empty(n, np.int64), np.empty(n, np.float32), np.empty(n, np.uint8)
+            self.L.eo_set_eval_log(_i(lid), _f(ld), lb.ctypes.data_as(u8ptr), n)
+        try:
+            ev = self.L.eo_search_impl(metric, _f(rows), rows.shape[1], n, _i(off), _i(nbr), _i(init_ids), _f(q), T, L, Lq,
+                                       I, set_l, visited.ctypes.data_as(u8ptr))
+        finally:
+            if log:
+                m = int(self.L.eo_eval_log_count())
+                self.L.eo_set_eval_log(None, None, None, 0)
         ms = (T - 1) * Lq
         ids = np.array([set_l[ms + i].id for i in range(L)], np.int64)
         ds = np.array([set_l[ms + i].dist for i in range(L)], np.float32)
+        if log:
+            assert m <= n, "the oracle logged %d evaluations over %d rows" % (m, n)
+            return ids, ds, ev, lid[:m].copy(), ld[:m].copy(), lb[:m].copy()
         return ids, ds, ev
 
     def search(self, metric, rows, n_indexed, off, nbr, nav, q, limit, T=1, L=500, Lq=None, I=15, prefilter=False,

@@ -337,6 +337,62 @@ static void pinned() {   // dim 768, T = 4, I = 15, prefilter over 768 columns, 
   }
 }
 
+// the filtered traversal's evaluation log, at the exact inputs of the repeat case of tests/filtered_walk_ref.py (REPEAT: 40000 x 16, 12 queries,
+// out-degree 96, T = 4, L = 180, I = 15): the first attempt's log is the floor of 16384 slots; the oracle's longest walk there evaluates 17497
+// rows, graph_search_impl asks the second attempt for min(n, 17497 + 17497 / 4 + 1024) = 22895 and the plan grants exactly that
+static TrvIn log_in(int64_t n, int64_t nq, int64_t L, int64_t ecap_min) {
+  TrvIn in = plan_in(n, nq, 16, L, L, 4, 15, 96, false);
+  in.filter_in_traversal = in.filtered = true;
+  in.ecap_min = ecap_min;
+  return in;
+}
+
+static void repeat_log() {
+  TrvPlan p;
+  Refusal r;
+  CHECK(trv_plan(log_in(40000, 12, 180, 0), &p, &r) == EPS_OK && p.ecap_plan == 16384 && p.slice == 12 && p.dp == 96);
+  CHECK(trv_plan(log_in(40000, 12, 180, 22895), &p, &r) == EPS_OK && p.ecap_plan == 22895 && p.slice == 12);
+  CHECK(trv_plan(log_in(40000, 12, 180, 50000), &p, &r) == EPS_OK && p.ecap_plan == 40000);                    // never beyond n: a walk evaluates a row once
+  CHECK(trv_plan(log_in(40000, 12, 256, 0), &p, &r) == EPS_OK && p.ecap_plan == 16384);                        // 64 L = the floor
+  CHECK(trv_plan(log_in(40000, 12, 257, 0), &p, &r) == EPS_OK && p.ecap_plan == 64 * 257);
+  CHECK(trv_plan(log_in(12000, 6, 2500, 0), &p, &r) == EPS_OK && p.ecap_plan == 12000);                        // clamped to the table
+  CHECK(trv_plan(log_in(2000, 24, 500, 0), &p, &r) == EPS_OK && p.ecap_plan == 2000);
+}
+
+// What two groups of tests/filtered_walk_ref.py rely on, on 256 CUs, at every out-degree a graph of theirs can have.
+// Group h's tiled step (2000 x 16, T = 4, L = 500, H_TILED = 1100 queries): 4 wavefronts per query, 4 workgroups per CU, 1024 workgroups in one
+// launch of 1100 queries - fewer than the queries, so workgroups walk a second query; the 300 queries of the unfiltered width case get one each.
+// Group e (12000 x 24, (T, L) = (4, 2500), (1, 12000) and (1, 9000)): a call of 6 queries keeps these queues in LDS (the 150 KB limit of up to 256
+// queries), the E_TILED = 264 queries of the tests send them to HBM (the 80 KB limit of a batch).
+static void shared_slots_and_hbm() {
+  TrvPlan p;
+  Refusal r;
+  for (int degree : {32, 50, 52, 60, 64})
+    for (int filtered = 0; filtered < 2; ++filtered) {
+      TrvIn in = plan_in(2000, 1100, 16, 500, 500, 4, 15, degree, false);
+      in.filter_in_traversal = in.filtered = filtered != 0;
+      CHECK(trv_plan(in, &p, &r) == EPS_OK && p.nw == 4 && p.per_cu == 4 && p.slots == 1024 && p.slots < in.nq && p.slice == 1100 && !p.qglobal);
+      in.nq = 300;
+      CHECK(trv_plan(in, &p, &r) == EPS_OK && p.slots == 300 && p.slice == 300);
+      for (int which = 0; which < 3; ++which) {
+        const int64_t eL = which == 0 ? 2500 : (which == 1 ? 12000 : 9000);
+        TrvIn e = plan_in(12000, 264, 24, eL, eL, which ? 1 : 4, 15, std::max(degree, 50), false);
+        e.filter_in_traversal = e.filtered = filtered != 0;
+        CHECK(trv_plan(e, &p, &r) == EPS_OK && p.qglobal && p.nw == 8 && p.slots == 264 && p.slice == 264 && p.ecap_plan == 12000);
+        e.nq = 6;
+        CHECK(trv_plan(e, &p, &r) == EPS_OK && !p.qglobal && p.nw == 16 && p.slots == 6);
+      }
+    }
+}
+
+static int ecap_of(int64_t n, int64_t nq, int64_t L, int64_t ecap_min) {
+  TrvPlan p;
+  Refusal r;
+  if (n < 1 || nq < 1 || L < 1 || ecap_min < 0 || trv_plan(log_in(n, nq, L, ecap_min), &p, &r) != EPS_OK) return printf("bad arguments\n"), 2;
+  printf("%lld\n", (long long)p.ecap_plan);
+  return 0;
+}
+
 static void tails() {
   TailPlan t;
   Refusal r;
@@ -417,11 +473,14 @@ static int seeds_of_file(const char* path, int64_t L) {
 
 int main(int argc, char** argv) {
   if (argc == 4 && strcmp(argv[1], "seeds") == 0) return seeds_of_file(argv[2], atoll(argv[3]));
+  if (argc == 6 && strcmp(argv[1], "ecap") == 0) return ecap_of(atoll(argv[2]), atoll(argv[3]), atoll(argv[4]), atoll(argv[5]));
   seeds();
   repair();
   plan_sweep();
   refusals();
   pinned();
+  repeat_log();
+  shared_slots_and_hbm();
   tails();
   build_lds();
   if (failures) {

@@ -49,6 +49,26 @@ def test_seed_list_equals_the_oracles_prepare_init_ids(oracle, check_exe, tmp_pa
         assert got.shape == (L,) and np.array_equal(got, want), L
 
 
+def test_evaluation_log_sizes_of_the_filtered_cases_are_the_headers(oracle, check_exe):
+    """tests/filtered_walk_ref.py restates the size of the filtered traversal's evaluation log (first_log) to choose its repeat case on the CPU:
+    for every case of its list, and for the repeat case's second attempt, the header's trv_launch gives the same number."""
+    import filtered_walk_ref as fr
+    seen = set()
+    for c in fr.all_cases():
+        key = (c["n"], c["nq"], min(c["L"], c["n"]))
+        if key in seen:
+            continue
+        seen.add(key)
+        r = run(check_exe, "ecap", str(key[0]), str(key[1]), str(key[2]), "0")
+        assert r.returncode == 0 and int(r.stdout) == fr.first_log(key[0], key[2]), (key, r.stdout, r.stderr[-2000:])
+    g = fr.cases_g()[0]
+    init, walks = fr.logged_walks(oracle, g)
+    need = fr.repeat_log(g["n"], max(w[2] for w in walks))
+    assert need == fr.REPEAT_SECOND_LOG       # (the figure pinned in graph_host_check.cpp repeat_log())
+    r = run(check_exe, "ecap", str(g["n"]), str(g["nq"]), str(g["L"]), str(need))
+    assert r.returncode == 0 and int(r.stdout) == need, (r.stdout, r.stderr[-2000:])
+
+
 def test_the_header_holds_no_device_type():
     src = open(os.path.join(ROOT, "vectordb_amd", "csrc", "graph_host.hpp")).read()
     assert "hip" not in re.sub(r"//.*", "", src).replace("__HIPCC__", "").lower()

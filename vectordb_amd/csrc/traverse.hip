@@ -556,7 +556,8 @@ int32_t graph_search_impl(Index& ix, const float* dq, int64_t nq, int k, const e
   if (waves_s && in.waves == 0) in.waves = -1;   // (a value like any other that is not 4, 8 or 16: 4 wavefronts)
   trv_launch(in, &c.pl);
   c.ecap = c.filtered ? c.pl.ecap_plan : 0;
-  // the same result-count cap as the unfiltered path: min(n_indexed, limit, LocalQueueSize) (:872)
+  // the result-count cap min(n_indexed, limit, LocalQueueSize) (:872) WITHOUT SearchQueueSize, which the unfiltered path's cap also holds
+  // (tail_plan's K): the answer is cut from the evaluated rows, not from the queue, so limit > L may return more than L rows
   c.Kf = std::min<int64_t>(std::min<int64_t>(n, walk_limit > 0 ? walk_limit : k), p.local_queue);
 
   // ---- visited set (not reclaimable from here to the return of this call) and scratch
