@@ -28,6 +28,8 @@
  *   eps_index_search_among          the row-by-row loops in which SearchByAttribute judges a primary-key list or a geo index's id list
  *                                   (db/execution/vec_search_executor.cpp:966-1013), with a distance and a top-k on top: the k closest
  *                                   of the rows the CALLER names - the allow-list search, the second stage of a hybrid search
+ *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
+ *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -429,6 +431,53 @@ int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of
  * searches without a host sync inside it. */
 int32_t eps_index_kernel_times(eps_index* h, double* ms_out, int32_t cap);
+
+/* ---- Sparse-vector fields (SPARSE_VECTOR_FLOAT): the exact scan of a CSR table.  GetDistFunc returns GetL2DistSqr / GetCosineDist /
+ * GetInnerProductDist for such a field (db/index/index.cpp:22-34, db/vector.cpp:7-96) and BruteForceSearch calls them row by row
+ * (db/execution/vec_search_executor.cpp:742, :802).  A handle of its own kind: nothing of an eps_index applies to it.
+ *
+ * A table is n rows in CSR: offsets int64[n + 1] with offsets[0] = 0, non-decreasing, offsets[n] = nnz; indices int32[nnz], strictly increasing
+ * inside a row, 0 <= index < dim; values float[nnz] - the row checks of the reference's insert path (db/table_segment_mvp.cpp:526-550), except
+ * that an empty row is accepted.  A batch of queries has the same form.  For query j the search returns the k smallest (distance, id) keys over the
+ * rows whose bit in the deleted bitset is clear.  distance(row, query) is, bit for bit, what the reference's function returns for (v1 = row,
+ * v2 = query): EPS_METRIC_EUCLIDEAN -> GetL2DistSqr, COSINE -> GetCosineDist, DOT_PRODUCT -> GetInnerProductDist - one fp32 accumulator from 0.0f,
+ * the two-pointer merge in ascending index order, every product rounded before it is added (no fused multiply-add), L2 adding the unmatched
+ * squares of both sides in merged order; COSINE = 1 - dot / sqrtf(v1_prod * v2_prod) with both norms summed in stored order, so an empty row or
+ * query gives NaN.  Keys order as everywhere in the library: -0 equals +0, every NaN comes after +inf, ties are broken by id; a NaN row still
+ * counts as a row.
+ *
+ * create: 1 <= dim <= 2^31 - 1; status codes and the no-CPU-fallback rule (EPS_INFRA_UNEXPECTED_ERROR without a gfx950 device) as
+ * eps_index_create.  A NULL handle: EPS_USER_ERROR from every call.
+ * attach_csr: the three arrays all host (copied) or all device (borrowed: the caller keeps them alive and unchanged); a mixed set is
+ * EPS_USER_ERROR; 0 <= n < 2^31.  offsets[n] defines nnz (a device offsets array is read back for that one value).  Replaces any previous
+ * table and forgets the bitset.  The table is validated in one device pass over the resident arrays before a search can see it - a row's elements
+ * are read only after its own offsets were found ordered and inside [0, nnz], so no input makes a kernel read outside the three arrays; the pass
+ * also takes every row's sum of squares in stored order (COSINE's v1_prod, the bits a recomputation per pair would give).  A violation:
+ * EPS_USER_ERROR naming the first offending row, and the handle keeps the table it had.  The call synchronises the handle's stream.
+ * set_id_map / set_deleted: as eps_index_set_id_map / eps_index_set_deleted (host or device bits, nbytes >= ceil(n / 8) else EPS_USER_ERROR,
+ * NULL clears).  Int-column tests and filter programs are not served here: a caller folds them into the bitset.
+ * search: q_offsets is a HOST int64[nq + 1], checked on the host; q_indices / q_values both host (validated on the host, copied) or both device
+ * (validated by one small launch whose verdict the call reads back - ONE stream synchronisation - before it launches the scan).  A malformed
+ * query: EPS_USER_ERROR naming the query.  A query of more than 4096 non-zeros (its pairs are staged in LDS): EPS_DB_UNSUPPORTED_ERROR, before
+ * any launch.  1 <= k <= 1024 else EPS_USER_ERROR; nq = 0: EPS_OK, nothing touched; n = 0: counts 0.  ids_out [nq][k], dist_out [nq][k],
+ * counts_out [nq] (may be NULL): all host (the call synchronises) or all device (on the handle's stream, the caller synchronises); ids through
+ * the id map, unused slots -1 / +inf, counts = min(k, visible rows).  The call first waits for earlier work on the handle's stream (its staging
+ * buffers are reused).
+ * last_stats: dist_evals = n * nq (every row gets a distance; visibility is judged only for keys that would enter a list), main_kernel_rows = n,
+ * main_kernel_queries = nq, main_kernel_bits = 32, main_kernel_launches, kernel_ms / main_kernel_ms from events; everything else 0. */
+typedef struct eps_sparse_index eps_sparse_index;
+int32_t eps_sparse_index_create(int64_t dim, int32_t metric, int32_t device, eps_sparse_index** out);
+int32_t eps_sparse_index_destroy(eps_sparse_index* h);
+const char* eps_sparse_index_last_error(const eps_sparse_index* h);
+int32_t eps_sparse_index_set_stream(eps_sparse_index* h, void* hip_stream);
+int32_t eps_sparse_index_synchronize(eps_sparse_index* h);
+int32_t eps_sparse_index_attach_csr(eps_sparse_index* h, const int64_t* offsets, const int32_t* indices, const float* values, int64_t n);
+int64_t eps_sparse_index_row_count(const eps_sparse_index* h);
+int32_t eps_sparse_index_set_id_map(eps_sparse_index* h, int64_t base, int64_t stride);
+int32_t eps_sparse_index_set_deleted(eps_sparse_index* h, const uint8_t* bits, int64_t nbytes);
+int32_t eps_sparse_index_search(eps_sparse_index* h, const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq,
+                                int32_t k, int64_t* ids_out, float* dist_out, int32_t* counts_out);
+int32_t eps_sparse_index_last_stats(const eps_sparse_index* h, eps_search_stats* out);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

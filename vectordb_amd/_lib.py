@@ -33,6 +33,9 @@ EXPORTS = [
     "eps_exchange_unique_id", "eps_exchange_create", "eps_exchange_allgather_merge", "eps_exchange_times", "eps_exchange_info", "eps_exchange_last_error",
     "eps_exchange_create_direct", "eps_exchange_mailbox_export", "eps_exchange_mailbox_connect", "eps_exchange_direct_merge",
     "eps_exchange_destroy",
+    "eps_sparse_index_create", "eps_sparse_index_destroy", "eps_sparse_index_last_error", "eps_sparse_index_set_stream", "eps_sparse_index_synchronize",
+    "eps_sparse_index_attach_csr", "eps_sparse_index_row_count", "eps_sparse_index_set_id_map", "eps_sparse_index_set_deleted", "eps_sparse_index_search",
+    "eps_sparse_index_last_stats",
 ]
 
 # Engine-selection switches of the library (eps_set_tuning, include/epsilla_gfx950.h).  The library itself reads no environment
@@ -233,6 +236,19 @@ def load():
     L.eps_exchange_last_error.restype = C.c_char_p
     L.eps_exchange_destroy.argtypes = [vp]
     L.eps_exchange_destroy.restype = None
+    L.eps_sparse_index_create.argtypes = [i64, i32, i32, C.POINTER(vp)]
+    L.eps_sparse_index_destroy.argtypes = [vp]
+    L.eps_sparse_index_last_error.argtypes = [vp]
+    L.eps_sparse_index_last_error.restype = C.c_char_p
+    L.eps_sparse_index_set_stream.argtypes = [vp, vp]
+    L.eps_sparse_index_synchronize.argtypes = [vp]
+    L.eps_sparse_index_attach_csr.argtypes = [vp, vp, vp, vp, i64]
+    L.eps_sparse_index_row_count.argtypes = [vp]
+    L.eps_sparse_index_row_count.restype = i64
+    L.eps_sparse_index_set_id_map.argtypes = [vp, i64, i64]
+    L.eps_sparse_index_set_deleted.argtypes = [vp, vp, i64]
+    L.eps_sparse_index_search.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    L.eps_sparse_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     for name in EXPORTS:
         if getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = i32

@@ -47,6 +47,23 @@ static int32_t on_single_device(eps_index* h, const char* refusal, int32_t err_c
   }
 }
 
+// A sparse-vector handle (eps_sparse_index): the same rule - no exception crosses the ABI, the text stays in the handle.
+#define SIX(h) reinterpret_cast<eps::SparseIndex*>(h)
+template <class F>
+static int32_t on_sparse(eps_sparse_index* h, F&& f) {
+  if (!h) return EPS_USER_ERROR;
+  eps::SparseIndex* ix = SIX(h);
+  try {
+    return f(*ix);
+  } catch (const std::bad_alloc&) {
+    return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "out of host memory");
+  } catch (const std::exception& e) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, std::string("unexpected: ") + e.what());
+  } catch (...) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, "unexpected exception");
+  }
+}
+
 // The merges have no handle to keep a message in: a refusal names its reason on stderr, as a failed eps_index_create does.
 static int32_t merge_refused(const char* entry, const char* why, int32_t rc) {
   std::fprintf(stderr, "%s: %s\n", entry, why);
@@ -368,6 +385,60 @@ int32_t eps_merge_select(const int64_t* ids, const int64_t* counts, const int64_
   if (side == 0) return eps::merge_select_host(dev, ids, counts, totals, shards, len, skip, limit, out_ids, count_out, total_out);
   dev.launch(eps::merge_select_args(ids, counts, totals, shards, len, skip, limit, out_ids, count_out, total_out));
   return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
+}
+
+// ---- sparse-vector fields (sparse_index.cpp; kernels: sparse.hip)
+int32_t eps_sparse_index_create(int64_t dim, int32_t metric, int32_t device, eps_sparse_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (dim < 1 || dim > eps::SPARSE_MAX_DIM || metric < 0 || metric > 2) return EPS_USER_ERROR;
+  try {
+    eps::SparseIndex* ix = new eps::SparseIndex(dim, metric, device);
+    const int32_t rc = ix->init();
+    if (rc != EPS_OK) {
+      std::fprintf(stderr, "eps_sparse_index_create: %s\n", ix->last_error());
+      delete ix;
+      return rc;
+    }
+    *out = reinterpret_cast<eps_sparse_index*>(ix);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_sparse_index_destroy(eps_sparse_index* h) {
+  if (!h) return EPS_USER_ERROR;
+  try {
+    delete SIX(h);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+const char* eps_sparse_index_last_error(const eps_sparse_index* h) { return h ? reinterpret_cast<const eps::SparseIndex*>(h)->last_error() : "null handle"; }
+int32_t eps_sparse_index_set_stream(eps_sparse_index* h, void* s) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.set_stream(s); });
+}
+int32_t eps_sparse_index_synchronize(eps_sparse_index* h) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.synchronize(); });
+}
+int32_t eps_sparse_index_attach_csr(eps_sparse_index* h, const int64_t* offsets, const int32_t* indices, const float* values, int64_t n) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.attach_csr(offsets, indices, values, n); });
+}
+int64_t eps_sparse_index_row_count(const eps_sparse_index* h) { return h ? reinterpret_cast<const eps::SparseIndex*>(h)->row_count() : -1; }
+int32_t eps_sparse_index_set_id_map(eps_sparse_index* h, int64_t b, int64_t s) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.set_id_map(b, s); });
+}
+int32_t eps_sparse_index_set_deleted(eps_sparse_index* h, const uint8_t* bits, int64_t nbytes) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.set_deleted(bits, nbytes); });
+}
+int32_t eps_sparse_index_search(eps_sparse_index* h, const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq, int32_t k,
+                                int64_t* ids, float* dist, int32_t* counts) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.search(q_offsets, q_indices, q_values, nq, k, ids, dist, counts); });
+}
+int32_t eps_sparse_index_last_stats(const eps_sparse_index* h, eps_search_stats* out) {
+  if (!h || !out) return EPS_USER_ERROR;
+  return SIX(const_cast<eps_sparse_index*>(h))->last_stats(out);
 }
 
 int32_t eps_set_tuning(const char* name, const char* value) {

@@ -307,6 +307,55 @@ class Index : public IndexBase {
   friend int32_t graph_search_impl(Index&, const float*, int64_t, int, const eps_search_params&, u64*, int64_t*, int, int64_t);
 };
 
+// A sparse-vector field behind eps_sparse_index_* (sparse_index.cpp; kernels: sparse.hip): a CSR table in HBM, a deleted bitset, an id map, and
+// the exact scan.  A handle type of its own: nothing of a dense index applies to it.
+class SparseIndex {
+ public:
+  SparseIndex(int64_t dim, int metric, int device) : device_(device), dim_(dim), metric_(metric) {}
+  ~SparseIndex();
+  int32_t init();
+  int32_t set_stream(void* s);
+  int32_t synchronize();
+  int32_t attach_csr(const int64_t* offsets, const int32_t* indices, const float* values, int64_t n);
+  int64_t row_count() const { return t_.n; }
+  int32_t set_id_map(int64_t base, int64_t stride);
+  int32_t set_deleted(const uint8_t* bits, int64_t nbytes);
+  int32_t search(const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq, int32_t k, int64_t* ids_out, float* dist_out,
+                 int32_t* counts_out);
+  int32_t last_stats(eps_search_stats* out);
+  const char* last_error() const { return err_.c_str(); }
+  int32_t fail(int32_t code, const std::string& msg) {
+    err_ = msg;
+    return code;
+  }
+  int32_t hip_fail(hipError_t e, const char* what);
+  int device_;
+
+ private:
+  struct Table {   // a validated table: the three arrays (owned copies of host arrays, or the caller's device arrays) and the rows' sums of squares
+    DevBuf off_buf, idx_buf, val_buf, norms;
+    const int64_t* offsets = nullptr;
+    const int32_t* indices = nullptr;
+    const float* values = nullptr;
+    int64_t n = 0, nnz = 0, longest = 0;
+    void swap(Table& o);
+  };
+  // one validation launch over device-resident arrays and the read of its verdict (a stream sync)
+  int32_t validate(const char* who, const char* what, const int64_t* d_off, const int32_t* d_idx, const float* d_val, int64_t n, int64_t nnz, float* norms,
+                   int64_t* longest);
+  int64_t dim_;
+  int metric_;
+  hipStream_t stream_ = nullptr;
+  bool own_stream_ = false;
+  Table t_;
+  int64_t id_base_ = 0, id_stride_ = 1;
+  const uint8_t* d_deleted_ = nullptr;
+  DevBuf deleted_buf_, verdict_buf_, q_buf_, partial_buf_, run_buf_, out_buf_;
+  hipEvent_t ev0_ = nullptr, ev1_ = nullptr, evk0_ = nullptr, evk1_ = nullptr;
+  eps_search_stats stats_{};
+  std::string err_;
+};
+
 // engines implemented in their own translation units
 // approx = true: no exact re-rank, the top-k is selected on the fp16 keys (kNN-graph construction), filters ignored
 // bits: operand width of the filter pass - 8 (int8 mirror; falls back to 16 where the table does not fit an 8-bit grid or the

@@ -7,6 +7,7 @@
 #include "among_host.hpp"
 #include "device_common.hpp"
 #include "merge_host.hpp"
+#include "sparse_host.hpp"
 
 namespace eps {
 
@@ -201,6 +202,38 @@ struct AmongArgs {
 // the gather (in slices of AMONG_GRID_Y query tiles), then the merge of every query's partial lists into run_keys[nq][k]: sorted, unique
 void launch_among_gather(const AmongArgs& a, hipStream_t s);
 void launch_among_merge(const u64* partial, int W, int k, int64_t nq, u64* run_keys, hipStream_t s);
+
+// ---------------------------------------------------------------- sparse-vector scan (eps_sparse_index_*; sparse.hip, plan: sparse_host.hpp)
+struct SparseVerdict {          // what sparse_validate_kernel leaves: ~0 / 0 before the launch
+  u64 first_bad;                // min over offending rows of (row << 3 | SPARSE_BAD_*), or ~0
+  u64 longest;                  // the longest row
+};
+struct SparseValidateArgs {
+  const int64_t* offsets;       // [n + 1]
+  const int32_t* indices;       // [nnz]
+  const float* values;          // [nnz]
+  int64_t n, nnz, dim;
+  float* norms;                 // [n] every row's sum of squares, added in stored order, or null
+  SparseVerdict* verdict;
+};
+void launch_sparse_validate(const SparseValidateArgs& a, hipStream_t s);
+struct SparseScanArgs {
+  const int64_t* offsets;       // the table, as sparse_validate_kernel passed it
+  const int32_t* indices;
+  const float* values;
+  const float* norms;           // [n]
+  int64_t n;
+  int metric;
+  const int64_t* q_offsets;     // [nq + 1] the queries, validated
+  const int32_t* q_indices;
+  const float* q_values;
+  int64_t nq;
+  int k;
+  FilterSpec f;                 // the deleted bitset only
+  SparsePlan plan;
+  u64* partial;                 // [nq][plan.W][k] per-wavefront sorted lists
+};
+void launch_sparse_scan(const SparseScanArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch
