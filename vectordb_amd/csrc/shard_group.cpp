@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "index.hpp"
+#include "shard_host.hpp"
 
 namespace eps {
 
@@ -81,7 +82,7 @@ class ShardGroup : public IndexBase {
   }
 
   int G() const { return (int)shard_.size(); }
-  int64_t rows_of(int s, int64_t n) const { return n > s ? (n - s + G() - 1) / G() : 0; }
+  int64_t rows_of(int s, int64_t n) const { return shard_rows_of(s, n, G()); }
 
   void worker(int s) {
     (void)hipSetDevice(shard_[s]->device_);
@@ -130,10 +131,14 @@ class ShardGroup : public IndexBase {
   int32_t attach_rows(const float* rows, int64_t n) override {
     if (n < 0 || (n > 0 && !rows)) return fail(EPS_USER_ERROR, "attach_rows: bad arguments");
     if (is_device_ptr(rows)) return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: rows are ingested from host memory");
-    const int32_t rc = each([&](int s, Index& ix) { return ix.attach_rows_strided(rows + (int64_t)s * dim_, rows_of(s, n), (int64_t)G() * dim_); });
+    const int32_t rc = each([&](int s, Index& ix) {
+      const ShardRowsView v = shard_rows_view(rows, dim_, s, G());
+      return ix.attach_rows_strided(v.base, rows_of(s, n), v.pitch);
+    });
     if (rc == EPS_OK) {
       n_rows_ = n;
       for (int s = 0; s < G(); ++s) shard_rows_[(size_t)s] = rows_of(s, n);
+      return keep_deleted_if_it_covers(n);
     }
     return rc;
   }
@@ -150,7 +155,7 @@ class ShardGroup : public IndexBase {
     shard_rows_[(size_t)shard] = n_local;
     n_rows_ = 0;
     for (int64_t v : shard_rows_) n_rows_ += v;
-    return EPS_OK;
+    return EPS_OK;   // (a bitset that came for fewer rows: see deleted_is_stale)
   }
   int32_t clone_rows(IndexBase& src_base, int64_t n) override {
     ShardGroup* src = dynamic_cast<ShardGroup*>(&src_base);
@@ -162,6 +167,7 @@ class ShardGroup : public IndexBase {
     if (rc == EPS_OK) {
       n_rows_ = n;
       for (int s = 0; s < G(); ++s) shard_rows_[(size_t)s] = rows_of(s, n);
+      return keep_deleted_if_it_covers(n);
     }
     return rc;
   }
@@ -176,9 +182,10 @@ class ShardGroup : public IndexBase {
     // global row n_rows_ + j goes to shard (n_rows_ + j) mod G
     const int64_t n0 = n_rows_;
     const int32_t rc = each([&](int s, Index& ix) {
-      const int64_t first = ((s - n0) % G() + G()) % G();   // first j with (n0 + j) mod G == s
-      const int64_t cnt = n_new > first ? (n_new - first + G() - 1) / G() : 0;
-      return cnt ? ix.append_rows_strided(rows + first * dim_, cnt, (int64_t)G() * dim_) : EPS_OK;
+      const ShardSpan a = shard_append_span(s, n0, n_new, G());
+      if (!a.count) return (int32_t)EPS_OK;
+      const ShardRowsView v = shard_rows_view(rows, dim_, a.first, G());
+      return ix.append_rows_strided(v.base, a.count, v.pitch);
     });
     if (rc == EPS_OK) {
       n_rows_ += n_new;
@@ -188,24 +195,41 @@ class ShardGroup : public IndexBase {
   }
   int32_t set_id_map(int64_t, int64_t) override { return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the id map is the sharding itself"); }
   int32_t set_deleted(const uint8_t* bits, int64_t nbytes) override {
-    if (!bits || nbytes <= 0) return each([](int, Index& ix) { return ix.set_deleted(nullptr, 0); });
+    if (!bits || nbytes <= 0) {
+      deleted_bytes_ = 0;
+      return each([](int, Index& ix) { return ix.set_deleted(nullptr, 0); });
+    }
     if (is_device_ptr(bits)) return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the deleted bitset comes from host memory");
     if (nbytes < (n_rows_ + 7) / 8) return fail(EPS_USER_ERROR, "set_deleted: bitset shorter than ceil(rows/8) bytes");
-    return each([&](int s, Index& ix) {   // bit i of the table = bit i / G of shard i mod G
-      const int64_t ns = rows_of(s, n_rows_);
-      std::vector<uint8_t> local((size_t)(ns + 7) / 8, 0);
-      for (int64_t l = 0; l < ns; ++l) {
-        const int64_t i = l * G() + s;
-        if ((bits[i >> 3] >> (i & 7)) & 1) local[l >> 3] |= uint8_t(1u << (l & 7));
-      }
+    const int32_t rc = each([&](int s, Index& ix) {   // bit i of the table = bit i / G of shard i mod G
+      std::vector<uint8_t> local((size_t)(rows_of(s, n_rows_) + 7) / 8);
+      shard_split_bits(bits, n_rows_, s, G(), local.data());
       return ix.set_deleted(local.empty() ? nullptr : local.data(), (int64_t)local.size());
     });
+    // What search() needs to know of the caller's bitset, which the shards cannot tell on their own: a shard whose slice is all zero keeps none,
+    // and a shard that an append passes by does not grow.  As the plain index has it (Index::set_deleted), a bitset with no bit set in its live
+    // bytes is no bitset and never goes stale.
+    deleted_bytes_ = rc == EPS_OK && (n_rows_ == 0 || shard_any_byte(bits, (n_rows_ + 7) / 8)) ? nbytes : 0;
+    deleted_rows_ = n_rows_;
+    return rc;
   }
+  // A new table (attach_rows, clone_rows): as Index::attach_rows_strided, a bitset too short for it is dropped - on EVERY shard, also on those
+  // whose own slice would still be long enough - and a longer one stays.
+  int32_t keep_deleted_if_it_covers(int64_t n) {
+    if (deleted_bytes_ == 0 || deleted_bytes_ >= (n + 7) / 8) return EPS_OK;
+    deleted_bytes_ = 0;
+    return each([](int, Index& ix) { return ix.set_deleted(nullptr, 0); });
+  }
+  // The slices were cut for the rows the table held when the bitset came: for any row after those the shards have no bit, where the plain index
+  // would still read the caller's (until the table outgrows the bitset's bytes).  The group refuses from the first such row on - never later than
+  // the plain index, and never with an answer of its own.
+  bool deleted_is_stale() const { return deleted_bytes_ > 0 && n_rows_ > deleted_rows_; }
   int32_t set_int_filter(const void* column, int64_t stride, int32_t width, int32_t op, int64_t constant) override {
     if (op == EPS_OP_NONE || !column) return each([](int, Index& ix) { return ix.set_int_filter(nullptr, 0, 0, EPS_OP_NONE, 0); });
     if (is_device_ptr(column)) return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: filter columns come from host memory");
     return each([&](int s, Index& ix) {   // the shard's rows are every G-th row of the column: same memory, G x the stride
-      return ix.set_int_filter(static_cast<const char*>(column) + (int64_t)s * stride, stride * G(), width, op, constant);
+      const ShardColumnView v = shard_column_view(column, stride, s, G());
+      return ix.set_int_filter(v.base, v.stride, width, op, constant);
     });
   }
   int32_t set_filter_program(const eps_filter_op* ops, int32_t nops, const void* rows, int64_t stride, int64_t n_rows, int32_t flags) override {
@@ -213,7 +237,8 @@ class ShardGroup : public IndexBase {
     if (!rows || is_device_ptr(rows)) return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: attribute rows come from host memory");
     if (stride <= 0 || n_rows < n_rows_) return fail(EPS_USER_ERROR, "set_filter_program: attribute rows missing or shorter than the table");
     return each([&](int s, Index& ix) {   // the shard's rows are every G-th row: ONLY those are uploaded (packed at the original stride)
-      return ix.set_filter_program_pitched(ops, nops, static_cast<const char*>(rows) + (int64_t)s * stride, stride * G(), stride, rows_of(s, n_rows), flags);
+      const ShardAttrView v = shard_attr_view(rows, stride, n_rows, s, G());
+      return ix.set_filter_program_pitched(ops, nops, v.base, v.pitch, v.row_bytes, v.count, flags);
     });
   }
   int32_t build(int64_t n, const eps_build_params* p) override {   // every shard builds the graph of its own rows
@@ -256,6 +281,7 @@ class ShardGroup : public IndexBase {
     if (!queries || !ids || !dist) return fail(EPS_USER_ERROR, "search: null buffer");
     if (walk_limit) return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: candidate walks are per index");
     if (!split_ok()) return fail(EPS_USER_ERROR, "search: the shards' row counts are not a hash split of the table (attach_shard_rows on every shard first)");
+    if (deleted_is_stale()) return fail(EPS_USER_ERROR, "search: the deleted bitset is shorter than the table (rows were appended): call set_deleted again");
     // where the buffers live: host, or a device of the group (r4).  The merge runs on the device that holds the result buffers
     // (shard 0's for host results); ids / dist / counts must live together.
     const int q_dev = device_of(queries), r_dev = device_of(ids);
@@ -278,7 +304,7 @@ class ShardGroup : public IndexBase {
       cap_ = 0;
       if (hipSetDevice(mdev) != hipSuccess) return fail(EPS_INFRA_UNEXPECTED_ERROR, "hipSetDevice");
       // one gathered buffer: [G][ids int64[nk] | dist f32[nk]] (the layout eps_merge_topk_packed takes)
-      stride_ = (nk * 12 + 7) / 8 * 8;
+      stride_ = shard_gather_stride(nq, k);
       if (hipMalloc(&gathered_, stride_ * G()) != hipSuccess || hipMalloc(&m_ids_, nk * 8) != hipSuccess || hipMalloc(&m_dist_, nk * 4) != hipSuccess)
         return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (shard merge)");
       cap_ = nk;
@@ -289,7 +315,7 @@ class ShardGroup : public IndexBase {
         merge_done_ = nullptr;
       }
     }
-    stride_ = (nk * 12 + 7) / 8 * 8;   // (the gathered layout of THIS call; the buffer holds at least cap_ entries per shard)
+    stride_ = shard_gather_stride(nq, k);   // (the gathered layout of THIS call; the buffer holds at least cap_ entries per shard)
     local_ids_.resize((size_t)G());
     local_dist_.resize((size_t)G());
     local_cnt_.resize((size_t)G());
@@ -340,12 +366,7 @@ class ShardGroup : public IndexBase {
     if (e == hipSuccess) e = hipStreamSynchronize(s0);
     if (e != hipSuccess) return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string("shard merge: ") + hipGetErrorString(e));
     merge_pending_ = false;
-    if (counts)
-      for (int64_t q = 0; q < nq; ++q) {
-        int32_t c = 0;
-        while (c < k && ids[q * k + c] >= 0) ++c;
-        counts[q] = c;
-      }
+    if (counts) shard_counts_from_ids(ids, nq, k, counts);   // (what merge_shards_kernel's `found` gives the device-results path)
     return EPS_OK;
   }
 
@@ -402,6 +423,7 @@ class ShardGroup : public IndexBase {
   int64_t dim_;
   int metric_;
   int64_t n_rows_ = 0;
+  int64_t deleted_bytes_ = 0, deleted_rows_ = 0;   // the caller's bitset: its length (0: none, or no bit set) and the rows the table held when it came
   std::vector<std::unique_ptr<Index>> shard_;
   std::vector<int64_t> shard_rows_;   // rows every shard holds (attach_rows: the hash split; attach_shard_rows: as handed over)
   std::vector<DevBuf> local_ids_, local_dist_, local_cnt_, local_q_;

@@ -96,6 +96,13 @@ class GpuIndex:
             rows = np.ascontiguousarray(rows, np.float32)
         self._check(self.L.eps_index_append_rows(self.h, _ptr(rows), rows.shape[0]))
 
+    def clone_rows(self, src, n=None):
+        """eps_index_clone_rows: this index takes a device-side copy of the first n rows of `src` (None: all of them) - another index of the same
+        kind, dimension and device(s): a plain index from a plain one, a shard group from a group with as many shards.  Later appends to either side
+        leave the other unchanged."""
+        n = src.row_count if n is None else int(n)
+        self._check(self.L.eps_index_clone_rows(self.h, src.h, n))
+
     def load_table(self, path, primitive_offset, var_len_attrs, dense_dims, field):
         """eps_index_load_table: the reference's data_mvp.bin straight into HBM; returns the record count"""
         dims = (C.c_int64 * len(dense_dims))(*dense_dims)
