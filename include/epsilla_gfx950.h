@@ -29,7 +29,8 @@
  *                                   (db/execution/vec_search_executor.cpp:966-1013), with a distance and a top-k on top: the k closest
  *                                   of the rows the CALLER names - the allow-list search, the second stage of a hybrid search
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
- *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table
+ *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
+ *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -478,6 +479,36 @@ int32_t eps_sparse_index_set_deleted(eps_sparse_index* h, const uint8_t* bits, i
 int32_t eps_sparse_index_search(eps_sparse_index* h, const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq,
                                 int32_t k, int64_t* ids_out, float* dist_out, int32_t* counts_out);
 int32_t eps_sparse_index_last_stats(const eps_sparse_index* h, eps_search_stats* out);
+
+/* Inverted lists (postings) of the attached table: the table stored by column, so that a DOT_PRODUCT or COSINE query touches only the postings of
+ * its own terms.  GetInnerProduct and GetCosineDist (db/vector.cpp:11-47) add a product only on a matching index, into one fp32 accumulator that
+ * starts at 0.0f, in ascending index order - so a per-row accumulator that receives acc = acc + (row_value * query_value), the query's terms applied
+ * in ascending index order, the product rounded before it is added and nothing fused, holds the same bits.  GetL2DistSqr adds the unmatched squares
+ * of both sides in merged order and has no such form: EUCLIDEAN stays on the scan.  Opt-in; no other call changes what it does.
+ *
+ * The layout: col_offsets int64[dim + 1], col_offsets[0] = 0, non-decreasing, col_offsets[dim] = nnz; the postings of column c are
+ * rows[col_offsets[c] .. col_offsets[c + 1]) with their values; rows are strictly ascending inside a column and the value bits are the CSR's.  The
+ * image is owned by the handle, also where the CSR arrays are borrowed device arrays, and costs 8 * nnz + 8 * (dim + 1) bytes of device memory on
+ * top of the CSR (the build needs up to 16 * nnz more and frees them when it ends).
+ * build_inverted: builds the image of the attached table on the device (a stable sort of the CSR's elements by column) and synchronises.  No
+ * table: EPS_USER_ERROR.  An EUCLIDEAN handle: EPS_DB_UNSUPPORTED_ERROR.  dim > 2^24: EPS_DB_UNSUPPORTED_ERROR (the column directory is dense).
+ * Out of device memory: EPS_INFRA_UNEXPECTED_ERROR, and the handle goes on answering by the scan.  Calling it twice rebuilds.  n = 0 or nnz = 0:
+ * an empty image.
+ * drop_inverted: frees the image; without one EPS_OK.  attach_csr forgets the image as it forgets the bitset; set_deleted and set_id_map do not
+ * touch it.
+ * search, while an image exists on a DOT_PRODUCT or COSINE handle, runs on it: every documented property of eps_sparse_index_search holds
+ * unchanged - validation, limits, host and device buffers, k <= 1024, the 4096-term query limit, NaN ordering, counts, the id map, the deleted
+ * bitset and last_stats (dist_evals = n * nq, main_kernel_bits = 32, main_kernel_ms = the inverted launches) - and so does every returned bit.
+ * The two engines are compared on one handle by searching, drop_inverted, and searching again (a rebuild is one sort of the table); the
+ * eps_set_tuning table has no entry for them.
+ * inverted_info: any out pointer may be NULL.  *columns = dim while an image exists, else 0; *postings = nnz of the image; *longest_column = its
+ * longest column; *last_engine: 0 = none yet, 1 = scan, 2 = inverted lists (the engine of the last search).
+ * get_inverted: host copies of the layout, for tests and tools: col_offsets int64[dim + 1], rows int32[nnz], values float[nnz]; any may be NULL.
+ * Without an image: EPS_USER_ERROR. */
+int32_t eps_sparse_index_build_inverted(eps_sparse_index* h);
+int32_t eps_sparse_index_drop_inverted(eps_sparse_index* h);
+int32_t eps_sparse_index_inverted_info(const eps_sparse_index* h, int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine);
+int32_t eps_sparse_index_get_inverted(eps_sparse_index* h, int64_t* col_offsets, int32_t* rows, float* values);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

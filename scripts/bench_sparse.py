@@ -16,11 +16,18 @@ served by both indices in the same run - GpuIndex flat search (EPS_FLAT_AUTO) on
 distances differ in rounding (the dense kernels sum in another order, with fused multiply-adds), so the line reports how many top-1 ids agree, not
 equality.
 
-Usage: python scripts/bench_sparse.py [--rows 1000000] [--dim 30522] [--reps 7] [--dense-gb 8] [--out FILE]"""
+--engine scan|inverted|both and --metric EUCLIDEAN|COSINE|DOT_PRODUCT (one or more) pick what runs on the flagship table.  With `inverted` or `both`
+the handle builds its inverted lists (GpuSparseIndex.build_inverted, csrc/sparse_inverted.hip; DOT_PRODUCT and COSINE only) - the line of the build
+holds its wall time and the image's bytes - and the same batches run on them; with `both` the scan runs first on the same handle, before the
+lists exist, and every inverted line says whether ids, distance bits and counts equal the scan's.  --skip-dense leaves the dense comparison out.
+
+Usage: python scripts/bench_sparse.py [--rows 1000000] [--dim 30522] [--reps 7] [--dense-gb 8] [--engine scan] [--metric EUCLIDEAN] [--skip-dense]
+                                      [--out FILE]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -71,6 +78,9 @@ if __name__ == "__main__":
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--dense-gb", type=float, default=8.0)
+    ap.add_argument("--engine", choices=("scan", "inverted", "both"), default="scan")
+    ap.add_argument("--metric", nargs="+", choices=("EUCLIDEAN", "COSINE", "DOT_PRODUCT"), default=["EUCLIDEAN"])
+    ap.add_argument("--skip-dense", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -92,21 +102,42 @@ if __name__ == "__main__":
         return (torch.empty((b, k), dtype=torch.int64, device=dev), torch.empty((b, k), dtype=torch.float32, device=dev),
                 torch.empty((b,), dtype=torch.int32, device=dev))
 
-    def sparse_points(X, Q, n, dim, table):
-        ix = amd.GpuSparseIndex(dim, "EUCLIDEAN").use_torch_stream()
+    def sparse_points(X, Q, n, dim, table, metric="EUCLIDEAN", engine="scan"):
+        ix = amd.GpuSparseIndex(dim, metric).use_torch_stream()
         ix.attach_csr(*X)
         nnz = int(X[0][-1])
         res = {}
-        for b in batches:
-            q, o = head(Q, b), outs(b)
-            whole, main = median_ms(torch, ix, lambda: ix.search(q, k, out=o), a.reps)
-            tile = 1 if b == 1 else (2 if b == 2 else 4)
-            scan_bytes = ((b + tile - 1) // tile) * (8 * nnz + 8 * n)
-            emit(route="sparse scan", table=table, rows=n, dim=dim, nnz=nnz, nnz_per_row=round(nnz / n, 1), nnz_per_query=round(int(Q[0][b]) / b, 1), batch=b, k=k,
-                 kernel_ms=round(whole, 4), scan_ms=round(main, 4), queries_per_s=round(b / whole * 1e3, 1), scan_bytes=scan_bytes,
-                 scan_bytes_per_s=round(scan_bytes / main * 1e3, 0), hbm_fraction=round(scan_bytes / main * 1e3 / HBM_PEAK, 4), reps=a.reps,
-                 kernel="sparse_scan_kernel: one row per lane read straight from the CSR arrays, queries staged in LDS")
-            res[b] = o
+        if engine != "inverted" or metric == "EUCLIDEAN":   # (EUCLIDEAN has no inverted form: the scan is what there is to measure)
+            for b in batches:   # (no inverted lists yet: the handle answers by the scan)
+                q, o = head(Q, b), outs(b)
+                whole, main = median_ms(torch, ix, lambda: ix.search(q, k, out=o), a.reps)
+                tile = 1 if b == 1 else (2 if b == 2 else 4)
+                scan_bytes = ((b + tile - 1) // tile) * (8 * nnz + 8 * n + (4 * n if metric == "COSINE" else 0))
+                emit(route="sparse scan", metric=metric, table=table, rows=n, dim=dim, nnz=nnz, nnz_per_row=round(nnz / n, 1), nnz_per_query=round(int(Q[0][b]) / b, 1),
+                     batch=b, k=k, kernel_ms=round(whole, 4), scan_ms=round(main, 4), queries_per_s=round(b / whole * 1e3, 1), scan_bytes=scan_bytes,
+                     scan_bytes_per_s=round(scan_bytes / main * 1e3, 0), hbm_fraction=round(scan_bytes / main * 1e3 / HBM_PEAK, 4), reps=a.reps,
+                     last_engine=ix.inverted_info()["last_engine"],
+                     kernel="sparse_scan_kernel: one row per lane read straight from the CSR arrays, queries staged in LDS")
+                res[b] = o
+        if engine != "scan" and metric != "EUCLIDEAN":
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ix.build_inverted()   # (synchronises)
+            build_s = time.perf_counter() - t0
+            info = ix.inverted_info()
+            emit(route="inverted lists: build", metric=metric, table=table, rows=n, dim=dim, nnz=nnz, build_wall_ms=round(build_s * 1e3, 2),
+                 image_bytes=8 * nnz + 8 * (dim + 1), csr_bytes=8 * nnz + 8 * (n + 1), longest_column=info["longest_column"], postings=info["postings"])
+            for b in batches:
+                q, o = head(Q, b), outs(b)
+                whole, main = median_ms(torch, ix, lambda: ix.search(q, k, out=o), a.reps)
+                same = None
+                if b in res:
+                    same = bool(torch.equal(o[0], res[b][0]) and torch.equal(o[1].view(torch.int32), res[b][1].view(torch.int32)) and torch.equal(o[2], res[b][2]))
+                emit(route="inverted lists", metric=metric, table=table, rows=n, dim=dim, nnz=nnz, nnz_per_row=round(nnz / n, 1),
+                     nnz_per_query=round(int(Q[0][b]) / b, 1), batch=b, k=k, kernel_ms=round(whole, 4), inverted_ms=round(main, 4),
+                     queries_per_s=round(b / whole * 1e3, 1), reps=a.reps, last_engine=ix.inverted_info()["last_engine"], same_bits_as_scan=same,
+                     kernel="sparse_inverted_kernel: term at a time on the postings, per-row fp32 accumulators in LDS")
+                res[b] = o
         return ix, res
 
     # ---- the flagship shape
@@ -115,9 +146,12 @@ if __name__ == "__main__":
     X = make_csr(torch, gen, n, dim, 160, dev)
     Q = make_csr(torch, gen, 1024, dim, 40, dev)
     torch.cuda.synchronize()
-    ix, _ = sparse_points(X, Q, n, dim, "flagship")
-    ix.close()
+    for metric in a.metric:
+        ix, _ = sparse_points(X, Q, n, dim, "flagship", metric, a.engine)
+        ix.close()
     del X, Q, ix
+    if a.skip_dense:
+        sys.exit(0)
 
     # ---- beside the dense route, at a size the dense index holds
     dim2 = 8192

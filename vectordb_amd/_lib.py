@@ -35,7 +35,8 @@ EXPORTS = [
     "eps_exchange_destroy",
     "eps_sparse_index_create", "eps_sparse_index_destroy", "eps_sparse_index_last_error", "eps_sparse_index_set_stream", "eps_sparse_index_synchronize",
     "eps_sparse_index_attach_csr", "eps_sparse_index_row_count", "eps_sparse_index_set_id_map", "eps_sparse_index_set_deleted", "eps_sparse_index_search",
-    "eps_sparse_index_last_stats",
+    "eps_sparse_index_last_stats", "eps_sparse_index_build_inverted", "eps_sparse_index_drop_inverted", "eps_sparse_index_inverted_info",
+    "eps_sparse_index_get_inverted",
 ]
 
 # Engine-selection switches of the library (eps_set_tuning, include/epsilla_gfx950.h).  The library itself reads no environment
@@ -249,6 +250,10 @@ def load():
     L.eps_sparse_index_set_deleted.argtypes = [vp, vp, i64]
     L.eps_sparse_index_search.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
     L.eps_sparse_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
+    L.eps_sparse_index_build_inverted.argtypes = [vp]
+    L.eps_sparse_index_drop_inverted.argtypes = [vp]
+    L.eps_sparse_index_inverted_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+    L.eps_sparse_index_get_inverted.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = i32

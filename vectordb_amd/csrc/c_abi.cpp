@@ -387,7 +387,7 @@ int32_t eps_merge_select(const int64_t* ids, const int64_t* counts, const int64_
   return hipGetLastError() == hipSuccess ? EPS_OK : EPS_INFRA_UNEXPECTED_ERROR;
 }
 
-// ---- sparse-vector fields (sparse_index.cpp; kernels: sparse.hip)
+// ---- sparse-vector fields (sparse_index.cpp; kernels: sparse.hip, sparse_inverted.hip)
 int32_t eps_sparse_index_create(int64_t dim, int32_t metric, int32_t device, eps_sparse_index** out) {
   if (!out) return EPS_USER_ERROR;
   *out = nullptr;
@@ -439,6 +439,19 @@ int32_t eps_sparse_index_search(eps_sparse_index* h, const int64_t* q_offsets, c
 int32_t eps_sparse_index_last_stats(const eps_sparse_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;
   return SIX(const_cast<eps_sparse_index*>(h))->last_stats(out);
+}
+int32_t eps_sparse_index_build_inverted(eps_sparse_index* h) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.build_inverted(); });
+}
+int32_t eps_sparse_index_drop_inverted(eps_sparse_index* h) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.drop_inverted(); });
+}
+int32_t eps_sparse_index_inverted_info(const eps_sparse_index* h, int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine) {
+  if (!h) return EPS_USER_ERROR;
+  return reinterpret_cast<const eps::SparseIndex*>(h)->inverted_info(columns, postings, longest_column, last_engine);
+}
+int32_t eps_sparse_index_get_inverted(eps_sparse_index* h, int64_t* col_offsets, int32_t* rows, float* values) {
+  return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.get_inverted(col_offsets, rows, values); });
 }
 
 int32_t eps_set_tuning(const char* name, const char* value) {

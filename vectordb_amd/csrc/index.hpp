@@ -323,6 +323,11 @@ class SparseIndex {
   int32_t search(const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq, int32_t k, int64_t* ids_out, float* dist_out,
                  int32_t* counts_out);
   int32_t last_stats(eps_search_stats* out);
+  // the inverted lists of the attached table (sparse_inverted.hip): while they exist a DOT_PRODUCT / COSINE search sums term at a time on them
+  int32_t build_inverted();
+  int32_t drop_inverted();
+  int32_t inverted_info(int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine) const;
+  int32_t get_inverted(int64_t* col_offsets, int32_t* rows, float* values);
   const char* last_error() const { return err_.c_str(); }
   int32_t fail(int32_t code, const std::string& msg) {
     err_ = msg;
@@ -332,6 +337,17 @@ class SparseIndex {
   int device_;
 
  private:
+  struct Inverted {   // the table by column, owned by the handle also where the CSR is borrowed
+    DevBuf col_offsets, postings;
+    bool built = false;
+    int64_t nnz = 0, longest = 0;
+    void release() {
+      col_offsets.release();
+      postings.release();
+      built = false;
+      nnz = longest = 0;
+    }
+  };
   struct Table {   // a validated table: the three arrays (owned copies of host arrays, or the caller's device arrays) and the rows' sums of squares
     DevBuf off_buf, idx_buf, val_buf, norms;
     const int64_t* offsets = nullptr;
@@ -348,6 +364,8 @@ class SparseIndex {
   hipStream_t stream_ = nullptr;
   bool own_stream_ = false;
   Table t_;
+  Inverted inv_;
+  int32_t last_engine_ = 0;   // 0 none yet, 1 scan, 2 inverted lists
   int64_t id_base_ = 0, id_stride_ = 1;
   const uint8_t* d_deleted_ = nullptr;
   DevBuf deleted_buf_, verdict_buf_, q_buf_, partial_buf_, run_buf_, out_buf_;

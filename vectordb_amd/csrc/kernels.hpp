@@ -8,6 +8,7 @@
 #include "device_common.hpp"
 #include "merge_host.hpp"
 #include "sparse_host.hpp"
+#include "sparse_inv_host.hpp"
 
 namespace eps {
 
@@ -234,6 +235,38 @@ struct SparseScanArgs {
   u64* partial;                 // [nq][plan.W][k] per-wavefront sorted lists
 };
 void launch_sparse_scan(const SparseScanArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- inverted lists of a sparse table (eps_sparse_index_build_inverted; sparse_inverted.hip, plan: sparse_inv_host.hpp)
+struct SparseInvBuildArgs {
+  const int64_t* offsets;       // the validated CSR
+  const int32_t* indices;
+  const float* values;
+  int64_t n, nnz, dim;
+  int64_t* col_offsets;         // [dim + 1] out
+  SparsePosting* postings;      // [nnz] out: the CSR's elements in (column, row) order
+  SparsePosting* pairs;         // [nnz] scratch: the sort's payload ping-pongs between it and `postings`
+  int32_t* keys_a;              // [nnz] scratch (sparse_inv_bytes: unused below two passes)
+  int32_t* keys_b;              // [nnz] scratch (unused below three passes)
+  u64* table;                   // [256][sort blocks] scratch
+  u64* longest;                 // [1] out: the longest column (zeroed by the launcher)
+};
+hipError_t launch_sparse_inv_build(const SparseInvBuildArgs& a, hipStream_t s);
+struct SparseInvArgs {
+  const int64_t* col_offsets;   // the image
+  const SparsePosting* postings;
+  const float* norms;           // [n]
+  int64_t n;
+  int metric;                   // 1 COSINE, 2 DOT_PRODUCT
+  const int64_t* q_offsets;     // [nq + 1] the queries, validated
+  const int32_t* q_indices;
+  const float* q_values;
+  int64_t nq;
+  int k;
+  FilterSpec f;                 // the deleted bitset only
+  SparseInvPlan plan;
+  u64* partial;                 // [nq][plan.rows.W][k] per-wavefront sorted lists
+};
+void launch_sparse_inverted(const SparseInvArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch

@@ -1,4 +1,5 @@
-// Host side of the sparse-vector index (eps_sparse_index_*, see index.hpp; limits, checks and the launch plan: sparse_host.hpp; kernels: sparse.hip).
+// Host side of the sparse-vector index (eps_sparse_index_*, see index.hpp; limits, checks and the launch plan: sparse_host.hpp; kernels: sparse.hip;
+// the inverted lists: sparse_inv_host.hpp, sparse_inverted.hip).
 #include "index.hpp"
 
 #include <cstring>
@@ -145,6 +146,7 @@ int32_t SparseIndex::attach_csr(const int64_t* offsets, const int32_t* indices, 
   if (rc != EPS_OK) return rc;
   t_.swap(t);
   d_deleted_ = nullptr;   // a new table: the bitset of the previous one is forgotten
+  inv_.release();         // ... and its inverted lists
   return EPS_OK;
 }
 
@@ -207,7 +209,9 @@ int32_t SparseIndex::search(const int64_t* q_offsets, const int32_t* q_indices, 
 
   // ---- scratch: [q_offsets | a host batch's indices | values], partial lists, result keys, host results' device block
   const int64_t n = t_.n;
-  const SparsePlan plan = sparse_plan(n, nq, k, longest);
+  const bool inverted = inv_.built;   // (build_inverted refuses EUCLIDEAN; drop_inverted sends the handle back to the scan)
+  const SparseInvPlan iplan = sparse_inv_plan(n, nq, k, longest);
+  const SparsePlan plan = inverted ? iplan.rows : sparse_plan(n, nq, k, longest);
   const size_t off_bytes = (size_t)(nq + 1) * sizeof(int64_t), el_bytes = q_dev ? 0 : (size_t)qnnz * 4;
   const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float), out_bytes = ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
   HIP_TRY(hipStreamSynchronize(stream_));   // (the previous call's staging is read; its pageable copies are complete)
@@ -239,12 +243,34 @@ int32_t SparseIndex::search(const int64_t* q_offsets, const int32_t* q_indices, 
     d_dist = reinterpret_cast<float*>(out_buf_.as<char>() + ids_bytes);
     d_cnt = reinterpret_cast<int32_t*>(out_buf_.as<char>() + ids_bytes + dist_bytes);
   }
+  last_engine_ = inverted ? 2 : 1;
   HIP_TRY(hipEventRecord(ev0_, stream_));
   stats_.main_kernel_rows = n;
   stats_.main_kernel_queries = nq;
   stats_.main_kernel_bits = 32;
   stats_.dist_evals = n * nq;
-  if (n > 0) {
+  if (n > 0 && inverted) {
+    SparseInvArgs a;
+    a.col_offsets = inv_.col_offsets.as<int64_t>();
+    a.postings = inv_.postings.as<SparsePosting>();
+    a.norms = t_.norms.as<float>();
+    a.n = n;
+    a.metric = metric_;
+    a.q_offsets = d_qoff;
+    a.q_indices = d_qidx;
+    a.q_values = d_qval;
+    a.nq = nq;
+    a.k = k;
+    a.f = no_filter();
+    a.f.deleted = d_deleted_;
+    a.plan = iplan;
+    a.partial = partial_buf_.as<u64>();
+    HIP_TRY(hipEventRecord(evk0_, stream_));
+    launch_sparse_inverted(a, stream_);
+    HIP_TRY(hipEventRecord(evk1_, stream_));
+    launch_among_merge(a.partial, plan.W, k, nq, run_keys, stream_);
+    stats_.main_kernel_launches = (nq + SPARSE_GRID_Y - 1) / SPARSE_GRID_Y;
+  } else if (n > 0) {
     SparseScanArgs a;
     a.offsets = t_.offsets;
     a.indices = t_.indices;
@@ -277,6 +303,86 @@ int32_t SparseIndex::search(const int64_t* q_offsets, const int32_t* q_indices, 
     HIP_TRY(hipMemcpyAsync(dist, d_dist, dist_bytes, hipMemcpyDeviceToHost, stream_));
     if (counts) HIP_TRY(hipMemcpyAsync(counts, d_cnt, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
+  }
+  return EPS_OK;
+}
+
+// ---- the inverted lists
+int32_t SparseIndex::build_inverted() {
+  if (!t_.offsets) return fail(EPS_USER_ERROR, "build_inverted: no table attached");
+  if (metric_ == EPS_METRIC_EUCLIDEAN)
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "build_inverted: EUCLIDEAN is served by the scan only: L2 adds the unmatched squares of both sides in merged order, which has no "
+                                          "term-at-a-time form");
+  if (dim_ > SPARSE_INV_MAX_DIM)
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "build_inverted: dim " + std::to_string((long long)dim_) + " is above the limit of " + std::to_string((long long)SPARSE_INV_MAX_DIM) +
+                                              " columns (2^24): the column directory is dense");
+  SparseInvBytes bytes;
+  if (!sparse_inv_bytes(dim_, t_.nnz, &bytes)) return fail(EPS_DB_UNSUPPORTED_ERROR, "build_inverted: more than 2^40 non-zeros");
+  HIP_TRY(hipSetDevice(device_));
+  HIP_TRY(hipStreamSynchronize(stream_));   // (no search on the previous image is in flight when it goes)
+  inv_.release();                           // calling it twice rebuilds; a failure below leaves no image and the scan goes on answering
+  Inverted im;
+  DevBuf pairs, keys_a, keys_b, table;   // freed when the build ends
+  const auto some = [](int64_t b) { return (size_t)(b ? b : 16); };
+  if (!im.col_offsets.reserve((size_t)bytes.directory) || !im.postings.reserve(some(bytes.postings)) || !pairs.reserve(some(bytes.pairs)) ||
+      !keys_a.reserve(some(bytes.keys_a)) || !keys_b.reserve(some(bytes.keys_b)) || !table.reserve((size_t)bytes.table))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "build_inverted: out of device memory (the image costs 8 * nnz + 8 * (dim + 1) bytes, the build up to 16 * nnz more)");
+  SparseInvBuildArgs a;
+  a.offsets = t_.offsets;
+  a.indices = t_.indices;
+  a.values = t_.values;
+  a.n = t_.n;
+  a.nnz = t_.nnz;
+  a.dim = dim_;
+  a.col_offsets = im.col_offsets.as<int64_t>();
+  a.postings = im.postings.as<SparsePosting>();
+  a.pairs = pairs.as<SparsePosting>();
+  a.keys_a = keys_a.as<int32_t>();
+  a.keys_b = keys_b.as<int32_t>();
+  a.table = table.as<u64>();
+  a.longest = &verdict_buf_.as<SparseVerdict>()->longest;
+  HIP_TRY(launch_sparse_inv_build(a, stream_));
+  unsigned long long longest = 0;
+  HIP_TRY(hipMemcpyAsync(&longest, a.longest, sizeof(longest), hipMemcpyDeviceToHost, stream_));
+  HIP_TRY(hipStreamSynchronize(stream_));
+  std::swap(inv_.col_offsets.p, im.col_offsets.p);
+  std::swap(inv_.col_offsets.cap, im.col_offsets.cap);
+  std::swap(inv_.postings.p, im.postings.p);
+  std::swap(inv_.postings.cap, im.postings.cap);
+  inv_.built = true;
+  inv_.nnz = t_.nnz;
+  inv_.longest = (int64_t)longest;
+  return EPS_OK;
+}
+
+int32_t SparseIndex::drop_inverted() {
+  if (!inv_.built) return EPS_OK;
+  HIP_TRY(hipSetDevice(device_));
+  HIP_TRY(hipStreamSynchronize(stream_));
+  inv_.release();
+  return EPS_OK;
+}
+
+int32_t SparseIndex::inverted_info(int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine) const {
+  if (columns) *columns = inv_.built ? dim_ : 0;   // entries of the directory; 0: no image
+  if (postings) *postings = inv_.nnz;
+  if (longest_column) *longest_column = inv_.longest;
+  if (last_engine) *last_engine = last_engine_;
+  return EPS_OK;
+}
+
+int32_t SparseIndex::get_inverted(int64_t* col_offsets, int32_t* rows, float* values) {
+  if (!inv_.built) return fail(EPS_USER_ERROR, "get_inverted: no inverted lists (build_inverted first)");
+  HIP_TRY(hipSetDevice(device_));
+  HIP_TRY(hipStreamSynchronize(stream_));
+  if (col_offsets) HIP_TRY(hipMemcpy(col_offsets, inv_.col_offsets.p, (size_t)(dim_ + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if ((rows || values) && inv_.nnz > 0) {
+    std::vector<SparsePosting> host((size_t)inv_.nnz);
+    HIP_TRY(hipMemcpy(host.data(), inv_.postings.p, host.size() * sizeof(SparsePosting), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < host.size(); ++i) {
+      if (rows) rows[i] = host[i].row;
+      if (values) values[i] = host[i].value;
+    }
   }
   return EPS_OK;
 }

@@ -1,5 +1,5 @@
 """GpuSparseIndex: a sparse-vector field (SPARSE_VECTOR_FLOAT) over the C ABI's eps_sparse_index_* - a CSR table in HBM and its exact scan
-(csrc/sparse.hip).  numpy arrays are host buffers; anything exposing `data_ptr()` (a torch tensor on the GPU) is passed as a device pointer and
+(csrc/sparse.hip), optionally its inverted lists for dot and cosine (csrc/sparse_inverted.hip).  numpy arrays are host buffers; anything exposing `data_ptr()` (a torch tensor on the GPU) is passed as a device pointer and
 used in place.  Every dtype, shape and contiguity is checked here, before a pointer reaches the library."""
 import ctypes as C
 
@@ -155,6 +155,31 @@ class GpuSparseIndex:
         self._check(self.L.eps_sparse_index_search(self.h, _ptr(q_off), _ptr(q_idx) if nnz else None, _ptr(q_val) if nnz else None, nq, k, _ptr(ids),
                                                    _ptr(dist), _ptr(counts)))
         return ids, dist, counts
+
+    def build_inverted(self):
+        """eps_sparse_index_build_inverted: the attached table by column (8 * nnz + 8 * (dim + 1) bytes of device memory); DOT_PRODUCT and COSINE
+        searches then sum term at a time on it and return the scan's bits.  attach_csr forgets it."""
+        self._check(self.L.eps_sparse_index_build_inverted(self.h))
+
+    def drop_inverted(self):
+        self._check(self.L.eps_sparse_index_drop_inverted(self.h))
+
+    def inverted_info(self):
+        """{"built", "columns", "postings", "longest_column", "last_engine"}; last_engine: 0 none yet, 1 scan, 2 inverted lists"""
+        cols, post, longest, engine = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._check(self.L.eps_sparse_index_inverted_info(self.h, C.byref(cols), C.byref(post), C.byref(longest), C.byref(engine)))
+        return {"built": cols.value > 0, "columns": cols.value, "postings": post.value, "longest_column": longest.value, "last_engine": engine.value}
+
+    def inverted_arrays(self):
+        """eps_sparse_index_get_inverted: host copies (col_offsets int64[dim + 1], rows int32[nnz], values float32[nnz])"""
+        info = self.inverted_info()
+        if not info["built"]:
+            raise ValueError("inverted_arrays: no inverted lists (build_inverted first)")
+        off = np.empty(self.dim + 1, np.int64)
+        rows, values = np.empty(info["postings"], np.int32), np.empty(info["postings"], np.float32)
+        self._check(self.L.eps_sparse_index_get_inverted(self.h, off.ctypes.data, rows.ctypes.data if rows.size else None,
+                                                         values.ctypes.data if values.size else None))
+        return off, rows, values
 
     def stats(self):
         s = SearchStats()
