@@ -270,6 +270,8 @@ struct Chain {
   std::vector<int64_t> bounds;
   // 8-bit operands on v7: fragment-major copy + prologue inside query_prep8_kernel - two launches less per call
   bool prep_does_it_all() const { return i8 && version >= 7; }
+  // the stages run the 16x16x64 tile (mfma_filter_kernel_v7<2, FM_IDS, true>), which reads its own fragment-major copy; the seed pass keeps qf
+  bool tile16() const { return i8 && version >= 7 && nq > 128 && !approx; }
   const float* maxima(const HalfMirror& m) const { return i8 ? (fold ? m.scal8f.as<float>() : m.scal8.as<float>()) : m.scal.as<float>(); }
   u32* group_counters(const HalfMirror& m) const { return gsync ? m.gsync.as<u32>() : nullptr; }
 };
@@ -287,6 +289,7 @@ static int32_t plan_chain(Index& ix, HalfMirror& m, const float* dq, int64_t nq,
     return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
   c.version = (c.d_pad_h % 128 != 0 || c.d_pad_h < 256) ? 3 : 7;
   if (c.version >= 7 && !m.qf.reserve((size_t)b_pad * c.d_pad_h * 2)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
+  if (c.tile16() && !m.qf16.reserve((size_t)b_pad * c.d_pad_h * 2)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
   if (!m.gsync.reserve(1024)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "MFMA engine: out of device memory (scratch)");
   c.S0 = seed_rows(k);
   c.seeded = !(tune_int("EPS_MFMA_SEED", 1) == 0) && n > 4 * c.S0;
@@ -307,6 +310,7 @@ static int32_t prepare_queries(Index& ix, HalfMirror& m, const Chain& c) {
     Prep8Extra px;
     if (c.prep_does_it_all()) {
       px.qf = m.qf.as<signed char>();
+      if (c.tile16()) px.qf16 = m.qf16.as<signed char>();
       if (c.prologue) {   // thresholds = 0x7F800000 pairs (+inf as fp32; as the 8-bit pass's int32 thresholds: never passes - the padding entries keep it)
         px.T2 = reinterpret_cast<u64*>(m.T.p);
         px.n2 = c.b_pad / 2;
@@ -391,6 +395,7 @@ static void launch_filter(const HalfMirror& m, const Chain& c, FilterArgs f, hip
     return;
   }
   f.group_sync = c.group_counters(m);
+  if (c.tile16() && !f.dense && !f.cand_keys) f.qf = m.qf16.as<_Float16>();
   if (f.group_sync && f.dense && !c.prologue) (void)hipMemsetAsync(f.group_sync, 0, 1024, s);   // (stages: reset by threshold_kernel / the re-rank)
   if (c.nq <= 128) {   // one 128-query tile: half the padded MFMA work, the pass streams the mirror
     f.tiles_q = 1;

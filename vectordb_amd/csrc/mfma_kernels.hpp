@@ -359,6 +359,10 @@ constexpr int V7_CAPW = 128;   // entries of a wavefront's pending-candidate lis
 // 4-slot ring of 256 rows x 128 B | [2][256] start values | [4 wavefronts][4][64] query constants | pending lists (4 counters, 4 x V7_CAPW entries)
 constexpr size_t V7_LDS_BYTES = (size_t)4 * 256 * 128 + 2 * 256 * sizeof(float) + 4096 + 64 + 4 * V7_CAPW * (8 + 4);
 
+}  // namespace eps
+#include "mfma_tile16.hpp"
+namespace eps {
+
 // I8 (8-bit operands): a.xh / a.qf hold int8 [..][2 * d_pad] (d_pad counts 2-byte units in both forms), a.base_s the int32 accumulator
 // start of every row, a.T the int32 pass thresholds (a row passes iff its accumulator >= T), a.s the (negative) key units per
 // accumulator unit, a.qstat[q][3] the query's constant of the approximate distance = a.s * accumulator + constant.
@@ -366,6 +370,10 @@ constexpr size_t V7_LDS_BYTES = (size_t)4 * 256 * 128 + 2 * 256 * sizeof(float) 
 // a.tile0 / a.ntiles count such tiles.  (128-row tiles with two workgroups per CU measured 8 % slower: profiles/r4_flat_ab_epilogue_late.txt.)
 template <int JQ, int MODE, bool I8 = false>
 __global__ __launch_bounds__(256, 1) void mfma_filter_kernel_v7(FilterArgs a) {
+  if constexpr (JQ == 2 && MODE == FM_IDS && I8) {   // the throughput form of the 8-bit pass: its own tile on 16x16x64 MFMAs (mfma_tile16.hpp)
+    v7_tile16_ids(a);
+    return;
+  }
   constexpr int NRB = 8;                  // 32-row blocks per wavefront
   constexpr int TR = 32 * NRB;            // rows per tile
   constexpr int VI = V7_VI;               // row blocks whose accumulators live in arch VGPRs

@@ -14,6 +14,7 @@ struct HalfMirror {
   DevBuf xn_s;     // float [n_pad]  -|x|^2/2 (= xn / s for L2; -inf on padding rows): the accumulators' start values
   DevBuf zeros_s;  // float [n_pad]  0 (-inf on padding rows)
   DevBuf qf;       // _Float16 fragment-major copy of qh (what the v7 kernel reads)
+  DevBuf qf16;     // 8-bit queries, fragment-major in 16x16x64 order (what v7's 256-query row-id tile reads)
   DevBuf gsync;    // u32 [64]: v7 group arrival counters
   DevBuf sxh, sbase, sbase_u;   // seed sample: S0 rows spread evenly over [0, n) (fp16 rows, their base / s, their base)
   int64_t sample_version = -1, sample_n = 0, sample_rows = 0;
@@ -99,6 +100,7 @@ struct HalfMirror {
 // start state of a seeded call (seed_prologue_kernel).  All-null: plain query_prep8 (the traversal's prefilter).
 struct Prep8Extra {
   signed char* qf = nullptr;   // fragment-major copy: [b_pad/32][d_pad8/32][64 lanes][16 bytes]
+  signed char* qf16 = nullptr; // the same in 16x16x64 order: [b_pad/16][d_pad8/64][64 lanes][16 bytes] (the 256-query row-id tile, mfma_tile16.hpp)
   u64* T2 = nullptr;           // prologue: thresholds (pairs), n2 entries, value Tv
   int64_t n2 = 0;
   u64 Tv = 0;

@@ -385,8 +385,11 @@ __global__ __launch_bounds__(256) void query_prep8_kernel(const float* q, int64_
   signed char* dst = q8 + r * d_pad8;
   // where byte column c of row r lives in the fragment-major copy
   const int64_t fbase = x.qf ? ((r >> 5) * (int64_t)(d_pad8 >> 5)) * 1024 + (r & 31) * 16 : 0;
+  // ... and in the 16x16x64 copy: lane = query % 16 + 16 * (16-byte quarter of the K = 64 piece)
+  const int64_t fbase16 = x.qf16 ? ((r >> 4) * (int64_t)(d_pad8 >> 6)) * 1024 + (r & 15) * 16 : 0;
   auto fput = [&](int c, u32 v) {
     if (x.qf) *reinterpret_cast<u32*>(x.qf + fbase + (int64_t)(c >> 5) * 1024 + ((c >> 4) & 1) * 512 + (c & 15)) = v;
+    if (x.qf16) *reinterpret_cast<u32*>(x.qf16 + fbase16 + (int64_t)(c >> 6) * 1024 + ((c >> 4) & 3) * 256 + (c & 15)) = v;
   };
   if (r >= nq) {
     for (int c = lane * 4; c < d_pad8; c += 256) {
