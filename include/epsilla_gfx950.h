@@ -357,6 +357,41 @@ int32_t eps_index_mirror_view(eps_index* h, int32_t bits, const float* queries, 
 #define EPS_THR_DISTANCE 1
 int32_t eps_index_filter_pass(eps_index* h, const float* queries, int64_t nq, int32_t bits, int64_t row_lo, int64_t row_hi, int64_t cap, int32_t mode,
                               int32_t thr_form, const void* thr, void* T_out, uint32_t* cnt_out, void* cand_out);
+/* The pass of the one-pass search on its own, so that a test can hold what it leaves behind to an integer reference (tests/one_pass_ref.py,
+ * tests/test_gpu_one_pass_pin.py).  Single-device indices only; host arrays.  Does what the next eps_index_search(queries, nq, k, EPS_MODE_FLAT,
+ * EPS_FLAT_MFMA_I8) with default parameters would do up to and including the launch of the pass - the entry rule, the mirror's build or extension,
+ * the mask launch under a filter program, the prep launch (or none: the "clean" second call of 1-2 queries quantises them in the pass), the fold
+ * launch on a table that folds per-row margins, the pass in the form the shape selects - and NO re-rank launch, and copies out what the pass left:
+ *   form     which instantiation ran (below)
+ *   raw_cnt  [nq][waves]            entries every wavefront found for every query (counted beyond wave_cap)
+ *   raw      [nq][waves][wave_cap]  every wavefront's private list as stored: (accumulator << 32) | row; the first min(count, wave_cap) are valid
+ *   table    [nq][slots]            the final table of best accumulators (INT32_MIN: an empty slot)
+ *   qstat    [nq][4]                the queries' constants as the pass used them (clean form: as workgroup 0 of the pass wrote them)
+ *   kth, T_final [nq]               the k-th largest slot (INT32_MIN: fewer than k filled) and the threshold the re-rank's selection would apply,
+ *                                   computed on the device from the final table by the function that selection calls
+ * raw_cnt, raw and table are written densely for the `waves` and `slots` the form reports; the caller provides room for
+ * EPS_ONE_PASS_MAX_WAVES wavefronts, EPS_ONE_PASS_WAVE_CAP entries and EPS_ONE_PASS_MAX_SLOTS slots.
+ * EPS_DB_UNSUPPORTED_ERROR: that search would not take the one-pass form (the entry rule - fewer than 65 536 rows, dim > 1024, k > 64, nq > 32, more
+ * than 16 queries on a folding or a large table -, a form the table has been declined for, filtered calls being sent to the staged chain, a filter
+ * program that reads @distance, a table without a usable 8-bit mirror): a probe never runs anything else in its place.  Afterwards the next one-pass
+ * search starts with its prep launch; nothing else a later search could see changes (statistics, declined forms, the count of filtered calls to skip). */
+#define EPS_ONE_PASS_MAX_WAVES 8192
+#define EPS_ONE_PASS_WAVE_CAP 32
+#define EPS_ONE_PASS_MAX_SLOTS 128
+typedef struct eps_one_pass_form {
+  int32_t pieces;          /* 256-byte pieces of a mirror row: 2 | 3 | 4                                                   */
+  int32_t matrix;          /* 0: the v_dot4 kernel (1-4 queries), 1: the matrix-core kernel                                */
+  int32_t width;           /* v_dot4: queries the kernel is built for, 1 | 2 | 4; matrix: 16-query column blocks, 1 | 2    */
+  int32_t wide;            /* v_dot4 with the 128-slot table (k = 17..64, 1-2 queries)                                     */
+  int32_t prep_in_kernel;  /* the pass quantised its queries itself: no prep launch                                        */
+  int32_t slots, waves;    /* table slots per query (64 | 128); wavefronts of the launch                                   */
+  int32_t fold, rot;       /* per-row margins folded into the start values; the table's grid lies in the rotated frame     */
+  int32_t masked;          /* a filter program was evaluated into a bitset by the mask launch                              */
+  int32_t wave_cap;        /* entries a wavefront's list holds                                                             */
+  int32_t chunk;           /* consecutive rows a wavefront takes per step: row r belongs to wavefront (r / chunk) % waves  */
+} eps_one_pass_form;
+int32_t eps_index_one_pass_probe(eps_index* h, const float* queries, int64_t nq, int32_t k, eps_one_pass_form* form, uint32_t* raw_cnt, uint64_t* raw,
+                                 int32_t* table, float* qstat, int32_t* kth, int32_t* T_final);
 int32_t eps_index_set_graph(eps_index* h, int64_t n, const int64_t* offsets, const int64_t* neighbors,
                             int64_t navigation_point);
 int32_t eps_index_graph_info(const eps_index* h, int64_t* n, int64_t* edges, int64_t* navigation_point);

@@ -97,8 +97,10 @@ def test_public_header_is_plain_c_and_struct_layouts_match_ctypes(tmp_path, buil
 #include <stddef.h>
 #include "epsilla_gfx950.h"
 int main(void) {
-  printf("search %zu build %zu filter_op %zu %zu %zu %zu layout %zu\\n", sizeof(eps_search_params), sizeof(eps_build_params), sizeof(eps_filter_op),
-         offsetof(eps_filter_op, arg), offsetof(eps_filter_op, ival), offsetof(eps_filter_op, dval), sizeof(eps_table_layout));
+  printf("search %zu build %zu filter_op %zu %zu %zu %zu layout %zu one_pass_form %zu %zu %zu %d %d %d\\n", sizeof(eps_search_params), sizeof(eps_build_params),
+         sizeof(eps_filter_op), offsetof(eps_filter_op, arg), offsetof(eps_filter_op, ival), offsetof(eps_filter_op, dval), sizeof(eps_table_layout),
+         sizeof(eps_one_pass_form), offsetof(eps_one_pass_form, waves), offsetof(eps_one_pass_form, chunk), EPS_ONE_PASS_MAX_WAVES, EPS_ONE_PASS_WAVE_CAP,
+         EPS_ONE_PASS_MAX_SLOTS);
   return 0;
 }
 """)
@@ -111,6 +113,9 @@ int main(void) {
     assert C.sizeof(_lib.SearchParams) == c["search"] and C.sizeof(_lib.BuildParams) == c["build"]
     assert [C.sizeof(_lib.FilterOp), _lib.FilterOp.arg.offset, _lib.FilterOp.ival.offset, _lib.FilterOp.dval.offset] == c["fop"]
     assert C.sizeof(_lib.TableLayout) == c["layout"]
+    # eps_one_pass_form (eps_index_one_pass_probe) and the room its caller provides
+    assert [C.sizeof(_lib.OnePassForm), _lib.OnePassForm.waves.offset, _lib.OnePassForm.chunk.offset] == [int(x) for x in out[12:15]]
+    assert [_lib.ONE_PASS_MAX_WAVES, _lib.ONE_PASS_WAVE_CAP, _lib.ONE_PASS_MAX_SLOTS] == [int(x) for x in out[15:18]]
 
 
 

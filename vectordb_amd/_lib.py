@@ -26,7 +26,7 @@ EXPORTS = [
     "eps_default_search_params", "eps_default_build_params", "eps_index_create", "eps_index_create_sharded", "eps_index_destroy",
     "eps_index_last_error", "eps_index_last_error_class", "eps_index_set_stream", "eps_index_synchronize", "eps_index_attach_rows",
     "eps_index_append_rows", "eps_index_attach_shard_rows", "eps_index_clone_rows", "eps_index_row_count", "eps_index_load_table", "eps_index_set_id_map", "eps_index_set_deleted",
-    "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
+    "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
     "eps_index_get_graph", "eps_index_save_graph", "eps_index_load_graph", "eps_index_search", "eps_index_select", "eps_index_search_range", "eps_index_search_among",
     "eps_index_last_stats", "eps_index_kernel_times", "eps_normalize_rows", "eps_merge_topk", "eps_merge_topk_packed", "eps_set_tuning",
     "eps_merge_range", "eps_range_pack_bytes", "eps_merge_range_packed", "eps_merge_select", "eps_exchange_allgather_merge_range",
@@ -85,7 +85,7 @@ class _Synced:
     """The loaded library; calls that may consult a switch forward the environment first (see sync_tuning)."""
     _SYNC = frozenset(("eps_index_search", "eps_index_search_walk", "eps_index_build", "eps_index_knn_graph", "eps_index_link",
                        "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph",
-                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_search_range", "eps_index_search_among"))
+                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among"))
 
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
@@ -144,6 +144,12 @@ class MirrorView(C.Structure):
                     "x", "acc0", "acc0b", "erow", "hrow", "mu", "sp", "scal", "scalf", "qmax", "xn", "start", "q", "qstat")]
 
 
+class OnePassForm(C.Structure):
+    """eps_one_pass_form: which instantiation of the one-pass search's pass a probe ran"""
+    _fields_ = [(name, C.c_int32) for name in ("pieces", "matrix", "width", "wide", "prep_in_kernel", "slots", "waves", "fold", "rot", "masked", "wave_cap", "chunk")]
+
+
+ONE_PASS_MAX_WAVES, ONE_PASS_WAVE_CAP, ONE_PASS_MAX_SLOTS = 8192, 32, 128
 PASS_IDS, PASS_KEYS, PASS_DENSE = 0, 1, 2
 THR_RAW, THR_DISTANCE = 0, 1
 
@@ -203,6 +209,7 @@ def load():
     L.eps_index_link.argtypes = [vp, i64, vp, i64, C.POINTER(BuildParams), vp, vp, C.POINTER(i64)]
     L.eps_index_mirror_view.argtypes = [vp, i32, vp, i64, C.POINTER(MirrorView)]
     L.eps_index_filter_pass.argtypes = [vp, vp, i64, i32, i64, i64, i64, i32, i32, vp, vp, vp, vp]
+    L.eps_index_one_pass_probe.argtypes = [vp, vp, i64, i32, C.POINTER(OnePassForm), vp, vp, vp, vp, vp, vp]
     L.eps_index_set_graph.argtypes = [vp, i64, vp, vp, i64]
     L.eps_index_graph_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.eps_index_get_graph.argtypes = [vp, vp, vp]

@@ -232,6 +232,12 @@ int32_t eps_index_filter_pass(eps_index* h, const float* queries, int64_t nq, in
     return eps::flat_filter_pass(ix, queries, nq, bits, row_lo, row_hi, cap, mode, thr_form, thr, T_out, cnt_out, cand_out);
   });
 }
+int32_t eps_index_one_pass_probe(eps_index* h, const float* queries, int64_t nq, int32_t k, eps_one_pass_form* form, uint32_t* raw_cnt, uint64_t* raw,
+                                 int32_t* table, float* qstat, int32_t* kth, int32_t* T_final) {
+  return on_single_device(h, "one_pass_probe: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    return eps::one_pass_probe(ix, queries, nq, k, form, raw_cnt, reinterpret_cast<eps::u64*>(raw), table, qstat, kth, T_final);
+  });
+}
 int32_t eps_index_load_table(eps_index* h, const char* path, const eps_table_layout* layout, int64_t* n_out) {
   return on_single_device(h, "load_table: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) { return ix.load_table(path, layout, n_out); });
 }

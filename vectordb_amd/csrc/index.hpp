@@ -298,6 +298,7 @@ class Index : public IndexBase {
   int32_t fetch_to_host(const void* d_block, size_t block_bytes, std::initializer_list<HostPart> parts);
   friend int32_t quant8_view(Index&, Quant8View*);
   friend void quant8_queries(Index&, const Quant8View&, const float*, int64_t, signed char*, float*);
+  friend int32_t one_pass_probe(Index&, const float*, int64_t, int, eps_one_pass_form*, u32*, u64*, int32_t*, float*, int32_t*, int32_t*);
   friend int32_t flat_mfma_search(Index&, const float*, int64_t, int, u64*, bool, int);
   friend int32_t flat_mfma_search_slice(Index&, const float*, int64_t, int, u64*, bool, int, int, bool);
   friend struct BuildCtx;   // the stages of graph_build (graph_build.hip)
@@ -386,6 +387,9 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k);  // AUTO heuristi
 int32_t flat_mirror_view(Index& ix, int bits, const float* queries, int64_t nq, eps_mirror_view* v);
 int32_t flat_filter_pass(Index& ix, const float* queries, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
                          void* T_out, u32* cnt_out, void* cand_out);
+// the one-pass search up to and including its pass, and what that pass left behind (eps_index_one_pass_probe; one_pass.hip)
+int32_t one_pass_probe(Index& ix, const float* queries, int64_t nq, int k, eps_one_pass_form* form, u32* raw_cnt, u64* raw, int32_t* table, float* qstat,
+                       int32_t* kth, int32_t* T_final);
 // the matrix form of a radius search (Index::search_range): one filter launch per slice of queries with thresholds from L.radius, then the exact
 // tail into the survivor lists L; *cand_total += rows given an exact distance.  *served = false: no usable mirror - nothing was launched
 int32_t flat_range_lists(Index& ix, const float* dq, int64_t nq, int bits, const RangeLists& L, unsigned long long* cand_total, bool* served);

@@ -156,9 +156,23 @@ static void note_outcome(HalfMirror& m, int kclass, bool filtered, bool overflow
   }
 }
 
-// *done = false: not applicable to this call, or a list overflowed - the staged chain answers it
-int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool* done) {
-  *done = false;
+// What a call of the one-pass form is made of up to and including its pass: what the pass was launched with and what the re-rank launch behind it
+// (flat_stream8_slice) or a probe of its leavings (one_pass_probe) needs to know of it
+struct OnePass {
+  Stream8Args a;
+  FilterSpec fs;        // what the pass and the re-rank test rows with (a filter program: its mask, as a deleted bitset)
+  CallCounters c;
+  int64_t n = 0;        // rows scanned
+  int kclass = 0, slots = 0, cap = 0, pieces = 0;
+  bool filtered = false, masked = false, mfma_form = false, wide = false, clean = false, host_words = false, two_launches = false, timed = false;
+};
+
+// From the entry rule to the pass: the rule (one_pass_fits, declined forms, programs that read @distance, filtered calls sent to the chain), the
+// scratch, the mask launch under a filter program, the prep launch - or none where the last one-pass call left the state clean -, the fold launch
+// behind it on a folding table, and the pass itself.  *taken = false: the call does not take the form, nothing was launched.  probe: a look at
+// what the next search would do - what that search would consume (the count of filtered calls still to skip) stays as it is
+static int32_t one_pass_to_the_pass(Index& ix, const float* dq, int64_t nq, int k, bool probe, OnePass* p, bool* taken) {
+  *taken = false;
   HalfMirror& m = *ix.mirror_;
   const int64_t n = ix.scan_limit_ >= 0 ? std::min(ix.scan_limit_, ix.n_rows_) : ix.n_rows_;
   if (!one_pass_fits(ix, &m, nq, k, n)) return EPS_OK;
@@ -176,7 +190,7 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
   if (masked && tune_int("EPS_S8_FILTER_PROGRAMS", 1) == 0) return EPS_OK;   // (A/B switch: programs on the staged chain, as until r4)
   const bool filtered = fs.deleted || fs.column || masked;
   if (filtered && m.s8_filt_skip[kclass] > 0) {   // (a mask that starves the pass used to cost a wasted pass on EVERY call)
-    --m.s8_filt_skip[kclass];
+    if (!probe) --m.s8_filt_skip[kclass];
     return EPS_OK;
   }
   hipStream_t s = ix.stream_;
@@ -223,7 +237,7 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
   a.waves = (int)grid.x * 4;
   // (no event pair around the pass by default: a record between two dependent launches costs this chain 5-10 us each; kernel_ms covers
   // the call.  EPS_ONE_PASS_TIMED=1 - bench.py's roofline leg - records the pair: main_kernel_ms = the pass)
-  const bool timed = tune_int("EPS_ONE_PASS_TIMED", 0) != 0;
+  const bool timed = !probe && tune_int("EPS_ONE_PASS_TIMED", 0) != 0;
   if (timed) (void)hipEventRecord(ix.evk0_, s);
   const bool wide = slots != S8_SLOTS && nq <= 2;
   const int pieces = m.d_pad8 / 256;   // (rows of 512..1024 bytes)
@@ -231,7 +245,41 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
   else if (pieces == 3) launch_pass<3>(a, grid, s, wide, mfma_form, clean);
   else launch_pass<4>(a, grid, s, wide, mfma_form, clean);
   if (timed) (void)hipEventRecord(ix.evk1_, s);
-  RerankArgs ra = rerank_args(ix, m, dq, nq, k, fs, cap, run_keys, c, a.scal, 8);   // (fuse = 1: counts only - overflow / total)
+  p->a = a;
+  p->fs = fs;
+  p->c = c;
+  p->n = n;
+  p->kclass = kclass;
+  p->slots = slots;
+  p->cap = cap;
+  p->pieces = pieces;
+  p->filtered = filtered;
+  p->masked = masked;
+  p->mfma_form = mfma_form;
+  p->wide = wide;
+  p->clean = clean;
+  p->host_words = host_words;
+  p->two_launches = two_launches;
+  p->timed = timed;
+  *taken = true;
+  return EPS_OK;
+}
+
+// *done = false: not applicable to this call, or a list overflowed - the staged chain answers it
+int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool* done) {
+  *done = false;
+  HalfMirror& m = *ix.mirror_;
+  OnePass p;
+  bool taken = false;
+  const int32_t rc = one_pass_to_the_pass(ix, dq, nq, k, false, &p, &taken);
+  if (rc != EPS_OK || !taken) return rc;
+  const Stream8Args& a = p.a;
+  const CallCounters& c = p.c;
+  const int64_t n = p.n;
+  const int slots = p.slots;
+  const bool host_words = p.host_words, two_launches = p.two_launches;
+  hipStream_t s = ix.stream_;
+  RerankArgs ra = rerank_args(ix, m, dq, nq, k, p.fs, p.cap, run_keys, c, a.scal, 8);   // (fuse = 1: counts only - overflow / total)
   ra.s8_G = a.G;                 // (the launch selects its candidates from the pass's lists first)
   ra.s8_slots = slots;
   ra.s8_fast = !(tune_int("EPS_S8_RERANK", 1) == 0);   // (A/B switch: 0 = rerank_kernel with the selection prologue, as until r5)
@@ -258,7 +306,7 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
     m.s8_clean_g = m.s8g.p;
   }
   if (tune_env("EPS_DEBUG") || (h.overflow && tune_env("EPS_DEBUG_ONE_PASS_OVERFLOW"))) dump_one_pass(m, a, h);
-  note_outcome(m, kclass, filtered, h.overflow != 0, ix.rows_version_);
+  note_outcome(m, p.kclass, p.filtered, h.overflow != 0, ix.rows_version_);
   if (h.overflow) {   // (too loose a bound for this table, or a filter that leaves fewer than k rows visible: the staged chain answers)
     ix.result_finalized_ = false;
     return EPS_OK;
@@ -266,13 +314,99 @@ int32_t flat_stream8_slice(Index& ix, const float* dq, int64_t nq, int k, u64* r
   if (fin_here) ix.result_finalized_ = true;
   ix.stats_.rerank_rows += (int64_t)h.total;
   ix.stats_.dist_evals += nq * n;
-  ix.stats_.main_kernel_launches = timed ? 1 : 0;   // (0: not timed on its own)
+  ix.stats_.main_kernel_launches = p.timed ? 1 : 0;   // (0: not timed on its own)
   ix.stats_.main_kernel_rows = n;
   ix.stats_.main_kernel_queries = nq;
   ix.stats_.main_kernel_bits = 8;
   ix.stats_.one_pass = 1;
   ix.stats_.i8_rotated = m.rot8 ? 1 : 0;
   *done = true;
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the pass on its own (tests)
+// eps_index_one_pass_probe (include/epsilla_gfx950.h; tests/one_pass_ref.py, tests/test_gpu_one_pass_pin.py): what ONE pass leaves behind -
+// every wavefront's list, the table, the threshold the re-rank's selection would read from it - before any re-rank has looked at it.
+
+// kth and T of every query's FINAL table, by the function the re-rank's selection prologue calls (flat_kernels.hip), with its arguments
+__global__ __launch_bounds__(64) void one_pass_threshold_kernel(const int* G, int slots, int nq, int k, const float* qstat, const float* scal, int metric, float u, float slack,
+                                                                int* kth, int* T) {
+  const int lane = lane_id();
+  for (int q = 0; q < nq; ++q) {
+    int gk;
+    const int Tq = stream8_threshold_of(G + q * (slots * S8_SLOT_STRIDE), k, qstat + q * 4, scal, metric, u, slack, lane, gk, slots);
+    if (lane == 0) {
+      kth[q] = gk;
+      T[q] = Tq;
+    }
+  }
+}
+
+int32_t one_pass_probe(Index& ix, const float* hq, int64_t nq, int k, eps_one_pass_form* form, u32* raw_cnt, u64* raw, int32_t* table, float* qstat, int32_t* kth,
+                       int32_t* T_final) {
+  if (!hq || !form || !raw_cnt || !raw || !table || !qstat || !kth || !T_final) return ix.fail(EPS_USER_ERROR, "one_pass_probe: null argument");
+  if (nq < 1 || k < 1) return ix.fail(EPS_USER_ERROR, "one_pass_probe: nq and k must be positive");
+  if (ix.n_rows_ <= 0) return ix.fail(EPS_USER_ERROR, "no rows attached");
+  const char* not_this_form = "one_pass_probe: a search with these arguments would not take the one-pass form";
+  if (nq > S8_MAX_Q || k > S8_MAX_K) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, not_this_form);   // (before any mirror is built for it)
+  int32_t rc = ix.check_filters_cover_table("one_pass_probe");
+  if (rc != EPS_OK) return rc;
+  // the state a probe must hand back as it found it: the last search's statistics, and whether that search was a pre-filter call (this one is
+  // what a search with default parameters would be: it is not)
+  struct Guard {
+    Index& ix;
+    eps_search_stats stats;
+    bool prefilter;
+    ~Guard() {
+      ix.stats_ = stats;
+      ix.prefilter_call_ = prefilter;
+      if (ix.mirror_) ix.mirror_->s8_clean_cnt = ix.mirror_->s8_clean_g = nullptr;   // (the table is full and the lists are written: the next search starts with its prep launch)
+    }
+  } guard{ix, ix.stats_, ix.prefilter_call_};
+  ix.prefilter_call_ = false;
+  if (ix.prog_len_ > 0 && ix.prog_uses_dist_) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, not_this_form);   // (Index::search: the exact stream engine)
+  rc = ensure_mirror8(ix);
+  if (rc != EPS_OK) return rc;
+  HalfMirror& m = *ix.mirror_;
+  if (!m.i8_ok) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, not_this_form);
+  hipStream_t s = ix.stream_;
+  DevBuf dq, out;
+  if (!dq.reserve((size_t)nq * ix.dim_ * 4) || !out.reserve((size_t)nq * 8)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "one_pass_probe: out of device memory");
+  hipError_t er = hipMemcpyAsync(dq.p, hq, (size_t)nq * ix.dim_ * 4, hipMemcpyHostToDevice, s);
+  if (er != hipSuccess) return ix.hip_fail(er, "one_pass_probe: queries");
+  OnePass p;
+  bool taken = false;
+  rc = one_pass_to_the_pass(ix, dq.as<float>(), nq, k, true, &p, &taken);
+  if (rc != EPS_OK) return rc;
+  if (!taken) return ix.fail(EPS_DB_UNSUPPORTED_ERROR, not_this_form);
+  const Stream8Args& a = p.a;
+  int* d_kth = out.as<int>();
+  int* d_T = d_kth + nq;
+  hipLaunchKernelGGL(one_pass_threshold_kernel, dim3(1), dim3(64), 0, s, a.G, a.slots, a.nq, a.k, a.qstat, a.scal, a.metric, a.u, a.slack, d_kth, d_T);
+  er = hipGetLastError();
+  if (er != hipSuccess) return ix.hip_fail(er, "one_pass_probe: launch");
+  form->pieces = p.pieces;
+  form->matrix = p.mfma_form ? 1 : 0;
+  form->width = p.mfma_form ? (nq > 16 ? 2 : 1) : (nq > 2 ? 4 : (int32_t)nq);
+  form->wide = p.wide ? 1 : 0;
+  form->prep_in_kernel = p.clean ? 1 : 0;
+  form->slots = a.slots;
+  form->waves = a.waves;
+  form->fold = a.acc0_raw ? 1 : 0;
+  form->rot = m.rot8 ? 1 : 0;
+  form->masked = p.masked ? 1 : 0;
+  form->wave_cap = S8_WAVE_CAP;
+  form->chunk = p.mfma_form ? 16 : (p.pieces <= 3 ? 16 : 8);   // (stream8m_kernel: CH = 16; stream8_kernel: CH = 4 U, U = 4 | 2 at 4 pieces)
+  std::vector<int> g((size_t)nq * a.slots * S8_SLOT_STRIDE);
+  er = hipMemcpyAsync(g.data(), a.G, g.size() * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(raw_cnt, a.raw_cnt, (size_t)nq * a.waves * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(raw, a.raw, (size_t)nq * a.waves * S8_WAVE_CAP * 8, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(qstat, a.qstat, (size_t)nq * 16, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(kth, d_kth, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(T_final, d_T, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);   // (before the queries' device copy goes)
+  if (er != hipSuccess) return ix.hip_fail(er, "one_pass_probe");
+  for (size_t i = 0; i < (size_t)nq * a.slots; ++i) table[i] = g[i * S8_SLOT_STRIDE];
   return EPS_OK;
 }
 

@@ -31,6 +31,9 @@
 // int-column filter (calls with a compiled filter PROGRAM take the staged chain), and writes the caller-visible result.  Overflow of either list is reported through the re-rank's overflow counter and the
 // caller repeats the batch on the staged chain.  Rows with a FORCED start value (mirror_build.hip: ACC_FORCE) are always candidates and
 // never enter the table.
+//
+// What ONE pass leaves behind - the lists, the table, the threshold read from it - is pinned in integers, instantiation by instantiation, by
+// tests/test_gpu_one_pass_pin.py against tests/one_pass_ref.py (eps_index_one_pass_probe: one_pass.hip runs the call up to the pass and copies them out).
 #pragma once
 #include "device_common.hpp"
 #include "kernels.hpp"

@@ -320,6 +320,26 @@ class GpuIndex:
                 lists.append((u.view(np.float32), (c & np.uint64(0xFFFFFFFF)).astype(np.int64)))
         return cnt, lists, T
 
+    def one_pass_probe(self, queries, k):
+        """eps_index_one_pass_probe: what the next flat 8-bit search of `queries` with this k would do up to and including the one-pass search's
+        pass, and what that pass left behind - a dict: form (the eps_one_pass_form fields), raw_cnt [nq][waves] int64, raw [nq][waves][wave_cap]
+        uint64 ((accumulator << 32) | row as stored), table [nq][slots] int32, qstat [nq][4], kth [nq], T_final [nq] int32.  Raises
+        EpsillaError 50002 where that search would not take the one-pass form."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = len(q)
+        form = lib.OnePassForm()
+        room = min(max(nq, 1), 32)   # (more than 32 queries are refused before anything is written)
+        raw_cnt = np.empty(room * lib.ONE_PASS_MAX_WAVES, np.uint32)
+        raw = np.empty(room * lib.ONE_PASS_MAX_WAVES * lib.ONE_PASS_WAVE_CAP, np.uint64)
+        table = np.empty(room * lib.ONE_PASS_MAX_SLOTS, np.int32)
+        qstat = np.zeros((nq, 4), np.float32)
+        kth, T = np.zeros(nq, np.int32), np.zeros(nq, np.int32)
+        self._check(self.L.eps_index_one_pass_probe(self.h, _ptr(q), nq, int(k), C.byref(form), _ptr(raw_cnt), _ptr(raw), _ptr(table), _ptr(qstat), _ptr(kth), _ptr(T)))
+        f = {name: int(getattr(form, name)) for name, _ in lib.OnePassForm._fields_}
+        W, cap, S = f["waves"], f["wave_cap"], f["slots"]
+        return dict(form=f, k=int(k), raw_cnt=raw_cnt[:nq * W].reshape(nq, W).astype(np.int64), raw=raw[:nq * W * cap].reshape(nq, W, cap).copy(),
+                    table=table[:nq * S].reshape(nq, S).copy(), qstat=qstat, kth=kth, T_final=T)
+
     def select_edges(self, nodes, cands, depth=300, out_degree=50):
         """SyncPrune's sort + SelectEdge for given candidate lists (eps_index_select_edges); returns (ids [m][R] -1 padded, deg [m])"""
         nodes = np.ascontiguousarray(nodes, np.int64)
