@@ -40,7 +40,13 @@
  *                                   The reference has no counterpart of these: it does not shard a table
  *
  * Pointer arguments documented "host or device" are classified with hipPointerGetAttributes; device
- * pointers are used in place (no copy) on the index's stream.  Every function returns a status code
+ * pointers are used in place (no copy) on the index's stream.  WHEN an array is read:
+ *   - a HOST array passed to any call has been read when the call returns, whatever kind its outputs are (page-locked memory included: the
+ *     caller may refill it at once);
+ *   - a DEVICE array is read at the call's place in the index's stream (eps_index_set_stream) and must stay valid, and unchanged, until the
+ *     stream has reached that place; a device array a call installs (eps_index_attach_rows, _set_deleted, _set_int_filter,
+ *     _set_filter_program) is borrowed and read, in place, by every later call at ITS place in the stream.
+ * Every function returns a status code
  * from the reference's own table (utils/error.hpp:11-41): 0 = OK.  Calls on one handle must not overlap
  * (same contract as one VecSearchExecutor: one thread per executor instance); different handles are
  * independent.  The library never falls back to a CPU path: without a usable gfx950 device

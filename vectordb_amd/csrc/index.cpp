@@ -139,6 +139,16 @@ bool is_device_ptr(const void* p) {
   return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
+bool is_page_locked_ptr(const void* p) {
+  if (!p) return false;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {   // (memory the runtime has never seen: pageable)
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeHost;
+}
+
 Index::Index(int64_t dim, int metric, int device) : dim_(dim), metric_(metric), device_(device) {}
 
 Index::~Index() {

@@ -288,8 +288,12 @@ class Index : public IndexBase {
   // a call that reports statistics and takes a slot of the kernel ring (select takes neither: it leaves no trace)
   void begin_timed_call();
   void end_timed_call();   // the slot counts only when a main kernel ran
-  // *dq = queries where they are on the device already, else their upload in q_buf_
-  int32_t stage_queries(const char* who, const float* queries, int64_t nq, const float** dq);
+  // a caller's host array onto the device, on the stream.  The array has been read when the CALL returns (the header's rule): a copy out of
+  // page-locked memory is truly asynchronous, so where the call does not end in a stream sync of its own (call_syncs false: device results) the
+  // stream is synchronised here.  Pageable memory is staged by the runtime before hipMemcpyAsync returns.
+  int32_t copy_host_in(void* dst, const void* src, size_t bytes, bool call_syncs);
+  // *dq = queries where they are on the device already, else their upload in q_buf_ (call_syncs: see copy_host_in)
+  int32_t stage_queries(const char* who, const float* queries, int64_t nq, const float** dq, bool call_syncs);
   // one device block of results to up to four host arrays: part i is `bytes` bytes at `off` of the block (dst null: not asked for)
   struct HostPart {
     void* dst;
@@ -418,6 +422,7 @@ int32_t select_edges(Index& ix, const int64_t* nodes, int64_t m, const int64_t* 
 int32_t inter_insert(Index& ix, const int64_t* ids, const int32_t* deg, int64_t n, int32_t R, int64_t* out_ids, int32_t* out_deg);
 
 bool is_device_ptr(const void* p);
+bool is_page_locked_ptr(const void* p);   // host memory of hipHostMalloc / hipHostRegister (torch: pin_memory)
 
 inline eps_build_params build_params_or_default(const eps_build_params* p) {
   eps_build_params bp;

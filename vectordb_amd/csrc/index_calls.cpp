@@ -86,7 +86,13 @@ void Index::begin_timed_call() {
 }
 void Index::end_timed_call() { kring_valid_[kring_seq_ % KRING] = stats_.main_kernel_launches > 0; }
 
-int32_t Index::stage_queries(const char* who, const float* queries, int64_t nq, const float** dq) {
+int32_t Index::copy_host_in(void* dst, const void* src, size_t bytes, bool call_syncs) {
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream_));
+  if (!call_syncs && is_page_locked_ptr(src)) HIP_TRY(hipStreamSynchronize(stream_));   // the host array may change right after the call returns
+  return EPS_OK;
+}
+
+int32_t Index::stage_queries(const char* who, const float* queries, int64_t nq, const float** dq, bool call_syncs) {
   *dq = queries;
   if (is_device_ptr(queries)) return EPS_OK;
   const size_t qb = (size_t)nq * dim_ * sizeof(float);
@@ -99,7 +105,8 @@ int32_t Index::stage_queries(const char* who, const float* queries, int64_t nq, 
     memcpy(h_q_.p, queries, qb);
     HIP_TRY(hipMemcpyAsync(q_buf_.p, h_q_.p, qb, hipMemcpyHostToDevice, stream_));
   } else {
-    HIP_TRY(hipMemcpyAsync(q_buf_.p, queries, qb, hipMemcpyHostToDevice, stream_));
+    const int32_t rc = copy_host_in(q_buf_.p, queries, qb, call_syncs);
+    if (rc != EPS_OK) return rc;
   }
   *dq = q_buf_.as<float>();
   return EPS_OK;
@@ -141,7 +148,7 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
     return fail(EPS_USER_ERROR, "search: ids_out, dist_out and counts_out must all be host or all be device pointers");
 
   const float* dq;
-  rc = stage_queries("search", queries, nq, &dq);
+  rc = stage_queries("search", queries, nq, &dq, !out_dev);   // (host results: fetch_to_host ends the call in a sync)
   if (rc != EPS_OK) return rc;
 
   // mode selection of VecSearchExecutor::Search (vec_search_executor.cpp:855-935)
@@ -339,9 +346,9 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
   int32_t* d_sel = reinterpret_cast<int32_t*>(rng_in_.as<char>() + rad_bytes);
 
   const float* dq;
-  rc = stage_queries("search_range", queries, nq, &dq);
+  rc = stage_queries("search_range", queries, nq, &dq, true);   // (the sync below)
   if (rc != EPS_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(stream_));   // (the previous call's copies out of / into h_rng_ have completed)
+  HIP_TRY(hipStreamSynchronize(stream_));   // (the previous call's copies out of / into h_rng_ have completed - and this call's copy of host queries)
   memcpy(h_rad, radius, (size_t)nq * 4);
   HIP_TRY(hipMemcpyAsync(rng_in_.p, h_rad, (size_t)nq * 4, hipMemcpyHostToDevice, stream_));
   HIP_TRY(hipMemsetAsync(rng_cnt_.p, 0, rb_bytes, stream_));
@@ -491,7 +498,7 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
 
   const float* dq;
-  rc = stage_queries("search_among", queries, nq, &dq);
+  rc = stage_queries("search_among", queries, nq, &dq, !out_dev);
   if (rc != EPS_OK) return rc;
 
   // ---- scratch: [pair counter | offsets | a host list's ids], partial lists, result keys, host results' device block
@@ -507,10 +514,14 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   int64_t* d_off = cand_offsets ? among_in_.as<int64_t>() + 1 : nullptr;
   const int64_t* d_list = cand_ids;
   HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
-  if (cand_offsets) HIP_TRY(hipMemcpyAsync(d_off, cand_offsets, off_bytes, hipMemcpyHostToDevice, stream_));
+  if (cand_offsets) {
+    rc = copy_host_in(d_off, cand_offsets, off_bytes, !out_dev);
+    if (rc != EPS_OK) return rc;
+  }
   if (!ids_dev && n_cand > 0) {
     d_list = reinterpret_cast<const int64_t*>(among_in_.as<char>() + 8 + off_bytes);
-    HIP_TRY(hipMemcpyAsync(const_cast<int64_t*>(d_list), cand_ids, list_bytes, hipMemcpyHostToDevice, stream_));
+    rc = copy_host_in(const_cast<int64_t*>(d_list), cand_ids, list_bytes, !out_dev);
+    if (rc != EPS_OK) return rc;
   }
   u64* run_keys = run_buf_.as<u64>();
   int64_t* d_ids = ids;
