@@ -1,5 +1,6 @@
 // Stand-alone host check of csrc/graph_host.hpp - the seed list of a search, the connectivity repair and CSR assembly of the build, the launch plan
-// of the traversal with its refusals, the tail merge's arithmetic, the LDS bytes of the build's launches and their refusal - for a CPU build under -fsanitize=address,undefined
+// of the traversal with its refusals, the tail merge's arithmetic, the LDS bytes of the build's launches and their refusal, the LDS layouts of the three
+// kernels and the rule that judges the 8-bit prefilter - for a CPU build under -fsanitize=address,undefined
 // (tests/test_graph_host_cpu.py builds and runs it).  Every list lives in a heap block exactly as long as the library's, so an index beyond a
 // list is a heap overflow the sanitizer reports.
 //   graph_host_check                    all checks; prints "graph_host_check OK"
@@ -452,6 +453,118 @@ static void build_lds() {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ LDS layouts
+// the three byte totals as they stood before the layouts were structs, kept here as the reference
+static size_t old_prune_bytes(int dim, int R) {
+  return (size_t)((dim + 3) & ~3) * 4 + (size_t)PRUNE_POOL * 8 + (size_t)R * 8 + 64 * 4 + 16 + (size_t)4 * ((dim + 3) & ~3) * 4;
+}
+static size_t old_traverse_bytes(int dim, int Lp2, bool hashvis, bool prefilter, int cols8) {
+  const int qstride = (dim + 3) & ~3;
+  return (size_t)qstride * 4 + (size_t)Lp2 * 8 + TRV_CHUNK * 8 * 2 + TRV_CHUNK * 4 + 64 * 4 + (hashvis ? TRV_HASH * 4 : 0) +
+         (prefilter ? (size_t)(16 + 16 + (((cols8 > dim ? cols8 : dim) + 15) & ~15)) : 0);
+}
+static size_t old_traverse2_bytes(int dim, int T, int Lq, int64_t qtot, int dp, bool qglobal, bool prefilter, int cols8) {
+  const int qstride = (dim + 3) & ~3;
+  const size_t ecap = (size_t)T * dp;
+  const int wide = cols8 > dim ? cols8 : dim;
+  return (size_t)qstride * 4 + (qglobal ? (size_t)TRV2_SB : (size_t)qtot) * 8 + ecap * (8 + 8 + 4 + 4 + 4 + 4) + (size_t)traverse2_hash_slots(T, dp) * 8 +
+         ((qglobal || T == 1) ? 0 : (size_t)2 * Lq * 4) + (size_t)trv2_sh_ints(T) * 4 + (prefilter ? (size_t)(16 + 16 + ((wide + 15) & ~15)) : 0);
+}
+
+struct Field {
+  const char* name;
+  size_t at, bytes, align;
+};
+// the arrays of a layout in field order: ascending, disjoint, each aligned to its element type, the last one inside the total
+static void fields_fit(const std::vector<Field>& f, size_t total) {
+  size_t end = 0;
+  for (const Field& x : f) {
+    CHECK(x.at >= end);
+    CHECK(x.at % x.align == 0);
+    if (x.at < end || x.at % x.align) printf("  field %s at %zu (%zu bytes), previous end %zu\n", x.name, x.at, x.bytes, end);
+    end = x.at + x.bytes;
+  }
+  CHECK(end <= total);
+}
+static void inside(size_t at, size_t bytes, size_t align, size_t host, size_t host_bytes) {   // an overlay lies wholly inside the array it names
+  CHECK(at % align == 0 && at >= host && at + bytes <= host + host_bytes);
+}
+
+static void lds_layouts() {
+  const int dims[] = {1, 19, 32, 130, 768, 772, 1552, 8192};
+  for (int dim : dims) {
+    const size_t qrow = (size_t)((dim + 3) / 4 * 4) * 4;
+    const int cols_cases[] = {-1, dim, (dim + 255) / 256 * 256 + 256};   // prefilter off, on, on with cols8 > dim
+    for (int R : {50, 512}) {
+      const PruneLds l = prune_lds(dim, R);
+      fields_fit({{"sq", l.sq, qrow, 16}, {"pool", l.pool, (size_t)PRUNE_POOL * 8, 8}, {"kept", l.kept, (size_t)R * 4, 4}, {"keptd", l.keptd, (size_t)R * 4, 4},
+                  {"sh", l.sh, 64 * 4, 4}, {"sqb", l.sqb, PRUNE_PB * qrow, 16}},
+                 l.total);
+      CHECK(l.total == old_prune_bytes(dim, R) && prune_lds_bytes(dim, R) == l.total);
+    }
+    for (int cols8 : cols_cases) {
+      const bool pf = cols8 >= 0;
+      const size_t q8 = pf ? (size_t)((std::max(dim, cols8) + 15) / 16 * 16) : 0;
+      for (int Lp2 : {512, 2048})
+        for (int hash_in_lds = 0; hash_in_lds < 2; ++hash_in_lds) {
+          const TrvLds l = traverse_lds(dim, Lp2, hash_in_lds != 0, pf, pf ? cols8 : 0);
+          std::vector<Field> f = {{"sq", l.sq, qrow, 16},          {"queue", l.queue, (size_t)Lp2 * 8, 8},  {"newk", l.newk, TRV_CHUNK * 8, 8},
+                                  {"sorted", l.sorted, TRV_CHUNK * 8, 8}, {"work", l.work, TRV_CHUNK * 4, 4}, {"sh", l.sh, 64 * 4, 4},
+                                  {"hash", l.hash, hash_in_lds ? (size_t)TRV_HASH * 4 : 0, 4}};
+          if (pf) {
+            f.push_back({"qst", l.pf.qst, 16, 16});
+            f.push_back({"sq8", l.pf.sq8, q8, 16});
+            CHECK((size_t)q8_bytes(dim, cols8) == q8);
+          }
+          fields_fit(f, l.total);
+          inside(l.surv, TRV_CHUNK * 4, 4, l.sorted, TRV_CHUNK * 8);
+          CHECK(l.total == old_traverse_bytes(dim, Lp2, hash_in_lds != 0, pf, pf ? cols8 : 0) && traverse_lds_bytes(dim, Lp2, hash_in_lds != 0, pf, pf ? cols8 : 0) == l.total);
+        }
+      for (int T : {1, 2, 4, 17, 32, 128})
+        for (int dp : {8, 56, 64, 2048})
+          for (int qglobal = 0; qglobal < 2; ++qglobal) {
+            if (T * dp > 2048) continue;   // (trv_queues refuses it)
+            const int Lq = 137;
+            const int64_t qtot = (int64_t)(T - 1) * Lq + 512;
+            const size_t ecap = (size_t)T * dp, H = (size_t)traverse2_hash_slots(T, dp);
+            const Trv2Lds l = traverse2_lds(dim, T, Lq, qtot, dp, qglobal != 0, pf, pf ? cols8 : 0);
+            std::vector<Field> f = {{"sq", l.sq, qrow, 16},
+                                    {"qlds", l.qlds, (qglobal ? (size_t)TRV2_SB : (size_t)qtot) * 8, 8},
+                                    {"newk", l.newk, ecap * 8, 8},
+                                    {"sorted", l.sorted, ecap * 8, 8},
+                                    {"eid", l.eid, ecap * 4, 4},
+                                    {"eraw", l.eraw, ecap * 4, 4},
+                                    {"work", l.work, ecap * 4, 4},
+                                    {"npos", l.npos, ecap * 4, 4},
+                                    {"hid", l.hid, H * 4, 4},
+                                    {"hmin", l.hmin, H * 4, 4},
+                                    {"auxl", l.auxl, (qglobal || T == 1) ? 0 : (size_t)2 * Lq * 4, 4},
+                                    {"sh", l.sh, (size_t)trv2_sh_ints(T) * 4, 4}};
+            if (pf) {
+              f.push_back({"qst", l.pf.qst, 16, 16});
+              f.push_back({"sq8", l.pf.sq8, q8, 16});
+            }
+            fields_fit(f, l.total);
+            CHECK((size_t)l.H == H);
+            inside(l.eacc, ecap * 4, 4, l.newk, ecap * 8);
+            inside(l.wacc, ecap * 4, 4, l.newk, ecap * 8);
+            CHECK(l.wacc >= l.eacc + ecap * 4);
+            inside(l.wwk, ecap * 4, 4, l.sorted, ecap * 4);             // the first half of `sorted` ...
+            inside(l.surv, ecap * 4, 4, l.sorted + ecap * 4, ecap * 4);   // ... and its second half
+            CHECK(l.total == old_traverse2_bytes(dim, T, Lq, qtot, dp, qglobal != 0, pf, pf ? cols8 : 0));
+            CHECK(traverse2_lds_bytes(dim, T, Lq, qtot, dp, qglobal != 0, pf, pf ? cols8 : 0) == l.total);
+          }
+    }
+  }
+  // the scalar slots stay inside their arrays
+  CHECK(TRV_NODE + TRV_MAXM <= TRV_EDGE0 && TRV_EDGE0 + TRV_MAXM + 1 <= TRV_TQ && TRV_FP32 < TRV_WAVE && TRV_WAVE + 4 <= 64);
+  CHECK(PRN_WAVE + 4 <= PRN_POS && PRN_POS + PRUNE_PB <= PRN_KEPT_CLOSER && PRN_KEPT_CLOSER + PRUNE_PB <= PRN_PEER_CLOSER && PRN_PEER_CLOSER + PRUNE_PB * PRUNE_PB <= 64);
+  CHECK(TRV2_NEVAL < 16);
+  // the 60 % rule: more than 60 % of the neighbour evaluations still read the fp32 row -> the test does not pay; nothing evaluated: no verdict
+  CHECK(prefilter_pays(1000, 600) && !prefilter_pays(1000, 601) && prefilter_pays(1000, 0) && !prefilter_pays(1000, 1000));
+  CHECK(prefilter_pays(0, 0) && prefilter_pays(0, 5) && !prefilter_pays(5, 4) && prefilter_pays(5, 3));
+}
+
 // ------------------------------------------------------------------------------------------------ seeds of a graph in a file
 static int seeds_of_file(const char* path, int64_t L) {
   FILE* f = fopen(path, "rb");
@@ -483,6 +596,7 @@ int main(int argc, char** argv) {
   shared_slots_and_hbm();
   tails();
   build_lds();
+  lds_layouts();
   if (failures) {
     printf("graph_host_check: %d check(s) failed\n", failures);
     return 1;

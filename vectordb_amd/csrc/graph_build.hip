@@ -124,12 +124,14 @@ template <bool VEC4>
 __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int dim = a.dim;
-  const int qstride = (dim + 3) & ~3;
-  float* sq = reinterpret_cast<float*>(smem_raw);            // [qstride] V[v], later V[p]
-  u64* pool = reinterpret_cast<u64*>(sq + qstride);          // [PRUNE_POOL]
-  u32* kept = reinterpret_cast<u32*>(pool + PRUNE_POOL);     // [R]
-  float* keptd = reinterpret_cast<float*>(kept + a.R);       // [R]
-  int* sh = reinterpret_cast<int*>(keptd + a.R);             // [64] scalars, then the staged candidate vectors of the SelectEdge walk
+  const int qstride = lds_qstride(dim);
+  const PruneLds l = prune_lds(dim, a.R);
+  float* sq = reinterpret_cast<float*>(smem_raw + l.sq);
+  u64* pool = reinterpret_cast<u64*>(smem_raw + l.pool);
+  u32* kept = reinterpret_cast<u32*>(smem_raw + l.kept);
+  float* keptd = reinterpret_cast<float*>(smem_raw + l.keptd);
+  int* sh = reinterpret_cast<int*>(smem_raw + l.sh);
+  float* sqb = reinterpret_cast<float*>(smem_raw + l.sqb);
   const int tid = threadIdx.x;
   const int lane = lane_id();
   const int wave = tid >> 6;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   const int t = lane & (G - 1);
   constexpr int U = 4;
 
-  if (tid == 0) sh[0] = 0;
+  if (tid == 0) sh[PRN_FILL] = 0;
   for (int i = tid; i < PRUNE_POOL; i += 256) pool[i] = KEY_EMPTY;
   for (int i = tid; i < qstride; i += 256) sq[i] = i < dim ? a.rows[v * dim + i] : 0.f;
   __syncthreads();
@@ -161,16 +163,16 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   };
   if (total <= (u32)PRUNE_POOL) {
     for (u32 i = tid; i < total; i += 256) pool[i] = src_key(i);
-    if (tid == 0) sh[0] = (int)total;
+    if (tid == 0) sh[PRN_FILL] = (int)total;
   } else {
     // More keys than the pool holds (a hub of InterInsert): the pool is the PRUNE_POOL SMALLEST keys by (dist, id), repeats counted - not
     // the first arrivals.  T = the smallest key with |{key <= T}| >= PRUNE_POOL, found bit by bit; everything below T goes in, and copies of
     // T fill what is left: equal keys are one (dist, id), so which copies they are changes nothing.
     auto block_count = [&](int local) {
       for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-      if (lane == 0) sh[8 + wave] = local;
+      if (lane == 0) sh[PRN_WAVE + wave] = local;
       __syncthreads();
-      const int c = sh[8] + sh[9] + sh[10] + sh[11];
+      const int c = sh[PRN_WAVE] + sh[PRN_WAVE + 1] + sh[PRN_WAVE + 2] + sh[PRN_WAVE + 3];
       __syncthreads();
       return c;
     };
@@ -184,24 +186,24 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
     int local = 0;
     for (u32 i = tid; i < total; i += 256) local += src_key(i) < T ? 1 : 0;
     const int below = block_count(local);   // < PRUNE_POOL by the choice of T
-    if (tid == 0) sh[4] = 0;
+    if (tid == 0) sh[PRN_TIES] = 0;
     __syncthreads();
     for (u32 i = tid; i < total; i += 256) {
       const u64 key = src_key(i);
       if (key < T) {
-        pool[atomicAdd(&sh[0], 1)] = key;
+        pool[atomicAdd(&sh[PRN_FILL], 1)] = key;
       } else if (key == T) {
-        const int e = below + atomicAdd(&sh[4], 1);
+        const int e = below + atomicAdd(&sh[PRN_TIES], 1);
         if (e < PRUNE_POOL) pool[e] = key;
       }
     }
     __syncthreads();
-    if (tid == 0) sh[0] = PRUNE_POOL;
+    if (tid == 0) sh[PRN_FILL] = PRUNE_POOL;
   }
   __syncthreads();
   if (a.listB) {  // "avoid lose nearest neighbor in knng" (nsg.cpp:542-557): distances to the kNN list of v
     const u32* lst = a.listB + vrow * a.degB;
-    const int base = sh[0];
+    const int base = sh[PRN_FILL];
     for (int c0 = wave * RPW * U; c0 < a.degB; c0 += 4 * RPW * U) {
       const float* rp[U];
       u32 id[U];
@@ -229,30 +231,16 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
   // 512-entry queue + the kNN list, InterInsert's a few dozen entries - a quarter / a sixtieth of the 4096 slots
   int P2 = 64;
   {
-    const int filled = sh[0] + (a.listB ? a.degB : 0);
+    const int filled = sh[PRN_FILL] + (a.listB ? a.degB : 0);
     while (P2 < filled && P2 < PRUNE_POOL) P2 <<= 1;
   }
-  for (int size = 2; size <= P2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < (P2 >> 1); i += 256) {
-        const int lo = ((i / stride) * (stride << 1)) + (i % stride);
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const u64 x = pool[lo], y = pool[hi];
-        if ((x > y) == up) {
-          pool[lo] = y;
-          pool[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  for (int size = 2; size <= P2; size <<= 1) bitonic_passes<256>(pool, P2, 0, size, size >> 1);
   // ---- SelectEdge (nsg.cpp:655-685): walk unique candidates != v in order; keep p iff no kept r has dist(r,p) < dist(v,p)
   // count unique candidates first (needed for the "fits without pruning" case of InterInsert, nsg.cpp:640-650)
   if (tid == 0) {
-    sh[1] = 0;  // nk
-    sh[2] = 0;  // cursor
-    sh[3] = 0;  // pool positions passed (repeats not counted)
+    sh[PRN_NK] = 0;
+    sh[PRN_CURSOR] = 0;
+    sh[PRN_PASSED] = 0;
   }
   __syncthreads();
   const bool unlimited = a.depth <= 0;
@@ -264,57 +252,54 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
       if (key != KEY_EMPTY && key_id(key) != (u32)v && (i == 0 || pool[i - 1] != key)) ++local;
     }
     for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-    if (lane == 0) sh[8 + wave] = local;
+    if (lane == 0) sh[PRN_WAVE + wave] = local;
     __syncthreads();
-    uniq = sh[8] + sh[9] + sh[10] + sh[11];
+    uniq = sh[PRN_WAVE] + sh[PRN_WAVE + 1] + sh[PRN_WAVE + 2] + sh[PRN_WAVE + 3];
   }
   const bool keep_all = unlimited && uniq <= a.R;
   // The walk is sequential by definition (a candidate is judged against everything kept BEFORE it), but PB candidates are
   // evaluated per round: their vectors are staged in LDS, every kept row is streamed once against all of them (and the batch's
   // own rows against the later members of the batch), then one thread resolves the batch in order.  A quarter of the barriers
   // and of the row traffic of one candidate per round.
-  constexpr int PB = 4;
-  float* sqb = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(sh + 64) + 15) & ~(uintptr_t)15);   // [PB][qstride] candidate vectors (16-B aligned)
-  // sh[16+b] pool position of batch member b, sh[24+b] "a row kept before the batch is closer", sh[32 + b*PB + b2] "batch member b2 (< b)
-  // is closer to member b than v is"
+  constexpr int PB = PRUNE_PB;
   while (true) {
     if (tid == 0) {   // the next <= PB unique candidates
-      int c = sh[2];
+      int c = sh[PRN_CURSOR];
       int nb = 0;
       // depth: the reference scans the positions 0 .. depth of its sorted pool (nsg.cpp:655-685: `cursor < depth && ++cursor < size`), the
-      // node's own position included when it is there - depth candidates then, depth + 1 when the node is not in its pool.  sh[3] counts
+      // node's own position included when it is there - depth candidates then, depth + 1 when the node is not in its pool.  sh[PRN_PASSED] counts
       // the positions of the pool without repeats that were passed.
-      while (nb < PB && c < P2 && (unlimited || sh[3] <= a.depth)) {
+      while (nb < PB && c < P2 && (unlimited || sh[PRN_PASSED] <= a.depth)) {
         const u64 key = pool[c];
         if (key == KEY_EMPTY) break;
         if (!(c > 0 && pool[c - 1] == key)) {
-          sh[3] += 1;
+          sh[PRN_PASSED] += 1;
           if (key_id(key) != (u32)v) {
-            sh[16 + nb] = c;
-            sh[24 + nb] = 0;
-            for (int b2 = 0; b2 < PB; ++b2) sh[32 + nb * PB + b2] = 0;
+            sh[PRN_POS + nb] = c;
+            sh[PRN_KEPT_CLOSER + nb] = 0;
+            for (int b2 = 0; b2 < PB; ++b2) sh[PRN_PEER_CLOSER + nb * PB + b2] = 0;
             ++nb;
           }
         }
         ++c;
       }
-      sh[2] = c;
-      sh[6] = nb;
+      sh[PRN_CURSOR] = c;
+      sh[PRN_NB] = nb;
     }
     __syncthreads();
-    const int nb = sh[6];
-    const int nk = sh[1];
+    const int nb = sh[PRN_NB];
+    const int nk = sh[PRN_NK];
     if (nb == 0 || nk >= a.R) break;
     if (!keep_all && (nk > 0 || nb > 1)) {
       for (int i = tid; i < PB * qstride; i += 256) {
         const int b2 = i / qstride, c = i - b2 * qstride;
-        const u32 pid = key_id(pool[sh[16 + (b2 < nb ? b2 : 0)]]);
+        const u32 pid = key_id(pool[sh[PRN_POS + (b2 < nb ? b2 : 0)]]);
         sqb[i] = c < dim ? a.rows[(int64_t)pid * dim + c] : 0.f;
       }
       __syncthreads();
       float pd[PB];
 #pragma unroll
-      for (int b2 = 0; b2 < PB; ++b2) pd[b2] = b2 < nb ? key_dist(pool[sh[16 + b2]]) : -1.f;
+      for (int b2 = 0; b2 < PB; ++b2) pd[b2] = b2 < nb ? key_dist(pool[sh[PRN_POS + b2]]) : -1.f;
       const int nrows = nk + nb - 1;   // kept rows, then batch members 0 .. nb-2 (member b is judged against members < b)
       for (int c0 = wave * RPW * U; c0 < nrows; c0 += 4 * RPW * U) {
         const float* rp[U];
@@ -325,7 +310,7 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
           ci[u] = c0 + u * RPW + g;
           ok[u] = ci[u] < nrows;
           const int cc = ok[u] ? ci[u] : 0;
-          const u32 rid = cc < nk ? kept[cc] : key_id(pool[sh[16 + (cc - nk)]]);
+          const u32 rid = cc < nk ? kept[cc] : key_id(pool[sh[PRN_POS + (cc - nk)]]);
           rp[u] = a.rows + (int64_t)rid * dim;
         }
         float acc[U][PB];
@@ -336,8 +321,8 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
 #pragma unroll
           for (int b2 = 0; b2 < PB; ++b2) {
             if (b2 >= nb || !(acc[u][b2] < pd[b2])) continue;
-            if (ci[u] < nk) sh[24 + b2] = 1;
-            else if (ci[u] - nk < b2) sh[32 + b2 * PB + (ci[u] - nk)] = 1;
+            if (ci[u] < nk) sh[PRN_KEPT_CLOSER + b2] = 1;
+            else if (ci[u] - nk < b2) sh[PRN_PEER_CLOSER + b2 * PB + (ci[u] - nk)] = 1;
           }
         }
       }
@@ -347,21 +332,21 @@ __global__ __launch_bounds__(256) void prune_kernel(PruneArgs a) {
       int k2 = nk;
       int accepted[PB];
       for (int b2 = 0; b2 < nb && k2 < a.R; ++b2) {
-        bool bad = sh[24 + b2] != 0;
-        for (int b3 = 0; b3 < b2 && !bad; ++b3) bad = accepted[b3] && sh[32 + b2 * PB + b3] != 0;
+        bool bad = sh[PRN_KEPT_CLOSER + b2] != 0;
+        for (int b3 = 0; b3 < b2 && !bad; ++b3) bad = accepted[b3] && sh[PRN_PEER_CLOSER + b2 * PB + b3] != 0;
         accepted[b2] = (keep_all || !bad) ? 1 : 0;
         if (accepted[b2]) {
-          const u64 pkey = pool[sh[16 + b2]];
+          const u64 pkey = pool[sh[PRN_POS + b2]];
           kept[k2] = key_id(pkey);
           keptd[k2] = key_dist(pkey);
           ++k2;
         }
       }
-      sh[1] = k2;
+      sh[PRN_NK] = k2;
     }
     __syncthreads();
   }
-  const int nk = sh[1];
+  const int nk = sh[PRN_NK];
   for (int i = tid; i < a.R; i += 256) {
     a.out_ids[vrow * a.R + i] = i < nk ? kept[i] : TRV_NONE;
     a.out_dist[vrow * a.R + i] = i < nk ? keptd[i] : 0.f;
@@ -742,20 +727,11 @@ int32_t BuildCtx::link_stage() {
   ta.log = logb.as<u64>();
   ta.log_cnt = logc.as<u32>();
   ta.log_cap = Lcap;
-  ta.x8 = nullptr;
-  ta.acc0 = q8v.acc0;
-  ta.scal8 = q8v.scal8;
-  ta.q8 = nullptr;
-  ta.qstat8 = nullptr;
-  ta.d_pad8 = q8v.d_pad8;
-  ta.cols8 = q8v.cols8;
-  ta.u8 = q8v.u;
-  ta.slack8 = prefilter_slack(dim, group_lanes(dim, vec4));
+  ta.p8 = prefilter8_args(q8v, prefilter, dim, vec4);
   if (prefilter) {
     if (!q8b.reserve((size_t)NB * q8v.d_pad8) || !qstat8b.reserve((size_t)NB * 16)) return ix.fail(EPS_INFRA_UNEXPECTED_ERROR, "build: out of device memory");
-    ta.x8 = q8v.x8;
-    ta.q8 = q8b.as<signed char>();
-    ta.qstat8 = qstat8b.as<float>();
+    ta.p8.q8 = q8b.as<signed char>();
+    ta.p8.qstat8 = qstat8b.as<float>();
   }
   PruneArgs pa;
   std::memset(&pa, 0, sizeof(pa));
@@ -777,15 +753,14 @@ int32_t BuildCtx::link_stage() {
     if (prefilter) quant8_queries(ix, q8v, ta.queries, nb, q8b.as<signed char>(), qstat8b.as<float>());
     HIPCHK(launch_link_search(nb));
     if (v0 == 0 && prefilter && !tune_env("EPS_BUILD_PREFILTER") && n > NB) {
-      // judged on the first batch: where more than 60 % of the neighbour evaluations still read the fp32 row (distances small
-      // against the table's value range: clustered / low intrinsic dimension) the 8-bit test is pure overhead - off for the rest
+      // judged on the first batch (prefilter_pays, graph_host.hpp): off for the rest where the 8-bit test is pure overhead
       unsigned long long hc[4] = {0, 0, 0, 0};
       HIPCHK(hipMemcpyAsync(hc, counters.p, 32, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       const double nbr_evals = (double)hc[0] - (double)nb * Ls;
-      if (nbr_evals > 0 && (double)hc[3] > 0.6 * nbr_evals) {
+      if (!prefilter_pays(nbr_evals, (double)hc[3])) {
         prefilter = false;
-        ta.x8 = nullptr;
+        ta.p8.x8 = nullptr;
         if (debug) fprintf(stderr, "[eps build] Link: 8-bit prefilter switched off after the first batch (%.0f %% of the neighbour evaluations passed it)\n", 100.0 * (double)hc[3] / nbr_evals);
       }
     }
@@ -881,8 +856,8 @@ int32_t graph_build(Index& ix, int64_t n, const eps_build_params& bp, const Buil
   if (hook && hook->stop_after == 1) return c.export_knn();
   if ((rc = c.navigation_stage()) != EPS_OK) return rc;
   if ((rc = c.link_stage()) != EPS_OK) return rc;
-  if (hook && hook->stop_after == 2) return c.export_link();
   if ((rc = c.link_report()) != EPS_OK) return rc;
+  if (hook && hook->stop_after == 2) return c.export_link();
   // ---- 4. InterInsert
   rc = inter_insert_device(ix, c.nsg_ids.as<u32>(), c.nsg_dist.as<float>(), c.nsg_deg.as<u32>(), n, c.R, c.out_ids, c.out_dist, c.out_deg);
   if (rc != EPS_OK) return rc;

@@ -1,7 +1,7 @@
 // Host side of the graph unit (graph_build.hip, traverse.hip) that needs no device: the seed list of a search, the connectivity repair and the
-// CSR assembly of the build, the traversal's launch plan with its device-range refusals, the LDS layout of traverse2_kernel and the arithmetic
-// of the tail merge.  Plain C++ with no device type in it: the kernel sizes its LDS arrays through the layout helpers below, the same functions
-// tests/native/graph_host_check.cpp runs under a sanitizer.
+// CSR assembly of the build, the traversal's launch plan with its device-range refusals, the LDS layouts of prune_kernel, traverse_kernel and
+// traverse2_kernel and the arithmetic of the tail merge.  Plain C++ with no device type in it: the kernels carve their LDS arrays from the layout
+// structs below, the same functions tests/native/graph_host_check.cpp runs under a sanitizer.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -135,22 +135,118 @@ inline void lists_to_abi(const uint32_t* ids, const uint32_t* deg, int64_t rows,
   }
 }
 
-// ------------------------------------------------------------------------------------------------ LDS layout of the build's kernels
+// ------------------------------------------------------------------------------------------------ LDS layouts
+// One struct of byte offsets per kernel, computed by one function that the host sizes the launch with (total) and the kernel carves its
+// pointers from (smem_raw + l.field): an array the one side has and the other lacks cannot exist.  Offsets ascend in field order; a field
+// marked "over X" is an overlay - it names bytes of X that X does not use while the overlay is live.
+EPS_GRAPH_HD inline size_t lds_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+EPS_GRAPH_HD inline int lds_qstride(int dim) { return (dim + 3) & ~3; }   // floats of a staged row: dim rounded up to a 16-byte piece
+
+// The 8-bit prefilter's block, last in its kernel's layout: the query's four statistics, then the query on the mirror's 8-bit grid.  The block
+// starts on the next multiple of 16 at or behind `at`; `bytes` is what a launch with the block adds to its total, 16 of them for that round-up.
+EPS_GRAPH_HD inline int q8_bytes(int dim, int cols8) { return ((cols8 > dim ? cols8 : dim) + 15) & ~15; }   // the query on the grid
+struct Pf8Lds {
+  size_t qst;   // float [4] |q|^2, |q|, |q - qh|, C + c
+  size_t sq8;   // signed char [q8_bytes]
+  size_t bytes;
+};
+EPS_GRAPH_HD inline Pf8Lds pf8_lds(size_t at, int dim, int cols8) {
+  Pf8Lds l;
+  l.qst = lds_up16(at);
+  l.sq8 = l.qst + 16;
+  l.bytes = 16 + 16 + (size_t)q8_bytes(dim, cols8);
+  return l;
+}
+
+// ---- the build's kernels
 constexpr int PRUNE_POOL = 4096;   // sorted candidate pool per node of prune_kernel (LDS)
 constexpr int TRV_HASH = 8192;     // LDS visited hash slots of traverse_kernel (HASHVIS mode), power of two
 constexpr int TRV_CHUNK = 256;     // neighbours traverse_kernel handles per sub-round
 constexpr int BUILD_MAX_DIM = 8192;   // widest row the library accepts
+constexpr int PRUNE_PB = 4;        // candidates prune_kernel judges per round of its SelectEdge walk
 
-// prune_kernel: v's vector, pool, kept ids + distances, 64 scalars, 4 staged candidate vectors
-EPS_GRAPH_HD inline size_t prune_lds_bytes(int dim, int R) {
-  return (size_t)((dim + 3) & ~3) * 4 + (size_t)PRUNE_POOL * 8 + (size_t)R * 8 + 64 * 4 + 16 + (size_t)4 * ((dim + 3) & ~3) * 4;
+struct PruneLds {
+  size_t sq;      // float [qstride] V[v]
+  size_t pool;    // u64 [PRUNE_POOL]
+  size_t kept;    // u32 [R] kept ids ...
+  size_t keptd;   // float [R] ... and their distances
+  size_t sh;      // int [64] scalars (PruneSlot)
+  size_t sqb;     // float [PRUNE_PB][qstride] staged candidate vectors of the SelectEdge walk, 16-byte aligned
+  size_t total;
+};
+EPS_GRAPH_HD inline PruneLds prune_lds(int dim, int R) {
+  const size_t qrow = (size_t)lds_qstride(dim) * 4;
+  PruneLds l;
+  l.sq = 0;
+  l.pool = l.sq + qrow;
+  l.kept = l.pool + (size_t)PRUNE_POOL * 8;
+  l.keptd = l.kept + (size_t)R * 4;
+  l.sh = l.keptd + (size_t)R * 4;
+  l.sqb = lds_up16(l.sh + 64 * 4);
+  l.total = l.sh + 64 * 4 + 16 + PRUNE_PB * qrow;   // (16: sqb's round-up)
+  return l;
 }
-// traverse_kernel: the query, the queue, two chunks of keys, a chunk of ids, 64 scalars, the visited hash (LDS form), the prefilter's block
+EPS_GRAPH_HD inline size_t prune_lds_bytes(int dim, int R) { return prune_lds(dim, R).total; }
+enum PruneSlot {   // prune_kernel's sh[]
+  PRN_FILL = 0,     // keys in the pool
+  PRN_NK = 1,       // edges kept
+  PRN_CURSOR = 2,   // next pool position of the walk
+  PRN_PASSED = 3,   // pool positions passed (repeats not counted)
+  PRN_TIES = 4,     // copies of the threshold key taken into an overfull pool
+  PRN_NB = 6,       // members of this round's batch
+  PRN_WAVE = 8,     // [4] per-wave counts
+  PRN_POS = 16,     // [PRUNE_PB] pool position of batch member b
+  PRN_KEPT_CLOSER = 24,   // [PRUNE_PB] "a row kept before the batch is closer to member b than v is"
+  PRN_PEER_CLOSER = 32,   // [PRUNE_PB][PRUNE_PB] "batch member b2 (< b) is closer to member b than v is"
+};
+
+struct TrvLds {
+  size_t sq;       // float [qstride] the query
+  size_t queue;    // u64 [Lp2]
+  size_t newk;     // u64 [TRV_CHUNK] unsorted keys of this sub-round
+  size_t sorted;   // u64 [TRV_CHUNK]
+  size_t surv;     // over sorted: u32 [TRV_CHUNK] ids that passed the 8-bit test (step 3a; `sorted` is written from step 4 on)
+  size_t work;     // u32 [TRV_CHUNK] surviving neighbour ids
+  size_t sh;       // int [64] scalars (TrvSlot)
+  size_t hash;     // u32 [TRV_HASH] visited hash, when it lives in LDS
+  Pf8Lds pf;       // prefilter only
+  size_t total;
+};
+EPS_GRAPH_HD inline TrvLds traverse_lds(int dim, int Lp2, bool hash_in_lds, bool prefilter, int cols8) {
+  TrvLds l;
+  l.sq = 0;
+  l.queue = l.sq + (size_t)lds_qstride(dim) * 4;
+  l.newk = l.queue + (size_t)Lp2 * 8;
+  l.sorted = l.newk + TRV_CHUNK * 8;
+  l.surv = l.sorted;
+  l.work = l.sorted + TRV_CHUNK * 8;
+  l.sh = l.work + TRV_CHUNK * 4;
+  l.hash = l.sh + 64 * 4;
+  const size_t end = l.hash + (hash_in_lds ? TRV_HASH * 4 : 0);
+  l.pf = pf8_lds(end, dim, cols8);
+  l.total = end + (prefilter ? l.pf.bytes : 0);
+  return l;
+}
 EPS_GRAPH_HD inline size_t traverse_lds_bytes(int dim, int Lp2, bool hashvis, bool prefilter = false, int cols8 = 0) {
-  const int qstride = (dim + 3) & ~3;
-  return (size_t)qstride * 4 + (size_t)Lp2 * 8 + TRV_CHUNK * 8 * 2 + TRV_CHUNK * 4 + 64 * 4 + (hashvis ? TRV_HASH * 4 : 0) +
-         (prefilter ? (size_t)(16 + 16 + (((cols8 > dim ? cols8 : dim) + 15) & ~15)) : 0);
+  return traverse_lds(dim, Lp2, hashvis, prefilter, cols8).total;
 }
+constexpr int TRV_MAXM = 16;   // expansions of traverse_kernel per round, at most
+enum TrvSlot {   // traverse_kernel's sh[]
+  TRV_NWORK = 0,    // ids to evaluate in this chunk
+  TRV_NSEL = 1,     // candidates selected this round
+  TRV_K = 2,        // first possibly-unchecked queue position
+  TRV_NNEW = 3,     // keys of this chunk that passed the bound
+  TRV_RMIN = 4,     // lowest insert position of this chunk
+  TRV_SELPOS = 5,   // position of the first selected candidate
+  TRV_HFILL = 6,    // fill of the visited hash
+  TRV_LOGFILL = 7,  // keys logged
+  TRV_NODE = 8,     // [TRV_MAXM] selected node ids
+  TRV_EDGE0 = 24,   // [TRV_MAXM + 1] first edge of every selected node
+  TRV_TQ = 41,      // prefilter threshold of this chunk
+  TRV_NSURV = 42,   // prefilter survivors of this chunk
+  TRV_FP32 = 43,    // fp32 rows read in step 3
+  TRV_WAVE = 48,    // [4] per-wave counts
+};
 
 struct Refusal {   // what IndexBase::fail takes
   int32_t code = EPS_OK, err_class = 0;
@@ -179,12 +275,19 @@ inline int32_t build_lds_check(int dim, int R, int Lp2, bool hashvis, bool prefi
 // ------------------------------------------------------------------------------------------------ LDS layout of traverse2_kernel
 constexpr int TRV2_SB = 4096;       // keys of the LDS staging block of the QGLOBAL bitonic sort
 constexpr int TRV2_MAXT = 128;      // the reference's limit for IntraQueryThreads (config/config.hpp:29)
-// ints of scalar scratch: 16 scalars, nine [TS] per-worker arrays, [16] per-wave counts, [TS + 16] edge offsets; TS = T rounded up to 16
+// ints of scalar scratch: 16 scalars (Trv2Slot), nine [TS] per-worker arrays, [16] per-wave counts, [TS + 16] edge offsets; TS = T rounded up to 16
 EPS_GRAPH_HD inline int trv2_tstride(int T) { return T <= 16 ? 16 : (T + 15) & ~15; }
 EPS_GRAPH_HD inline int trv2_sh_ints(int T) { return 48 + 10 * trv2_tstride(T); }
-// bytes of the prefilter's LDS block: the query's four statistics, the query on the 8-bit grid, alignment spare
-EPS_GRAPH_HD inline int trv2_q8len(int dim) { return (dim + 15) & ~15; }
-EPS_GRAPH_HD inline int trv2_pf_bytes(int dim) { return 16 + 16 + trv2_q8len(dim); }
+enum Trv2Slot {   // traverse2_kernel's sh[0..16)
+  TRV2_SCRATCH = 0,    // longest chunk count of a queue insert
+  TRV2_VLOG = 2,       // undo-log fill
+  TRV2_ANYSEL = 3,     // a worker selected a candidate this step
+  TRV2_PREFIX = 4,     // running prefix (PickTopMToWorkers, MergeAll)
+  TRV2_VLOG_OVER = 7,  // the undo log overflowed
+  TRV2_ELOG = 8,       // evaluations logged (elog)
+  TRV2_TQ = 9,         // prefilter threshold of this step
+  TRV2_NEVAL = 10,     // prefilter form: nodes to evaluate this step
+};
 // slots of the per-step table of edge owners: power of two >= 2*T*dp, 0 when T == 1
 EPS_GRAPH_HD inline int traverse2_hash_slots(int T, int dp) {
   if (T <= 1) return 0;
@@ -192,13 +295,61 @@ EPS_GRAPH_HD inline int traverse2_hash_slots(int T, int dp) {
   while (h < 2 * T * dp) h <<= 1;
   return h;
 }
-// LDS bytes of one workgroup; qglobal = queues in HBM
-EPS_GRAPH_HD inline size_t traverse2_lds_bytes(int dim, int T, int Lq, int64_t qtot, int dp, bool qglobal, bool prefilter = false, int cols8 = 0) {
-  const int qstride = (dim + 3) & ~3;
-  const size_t ecap = (size_t)T * dp;
-  return (size_t)qstride * 4 + (qglobal ? (size_t)TRV2_SB : (size_t)qtot) * 8 + ecap * (8 + 8 + 4 + 4 + 4 + 4) + (size_t)traverse2_hash_slots(T, dp) * 8 +
-         ((qglobal || T == 1) ? 0 : (size_t)2 * Lq * 4) + (size_t)trv2_sh_ints(T) * 4 + (prefilter ? (size_t)trv2_pf_bytes(cols8 > dim ? cols8 : dim) : 0);
+struct Trv2Lds {   // ecap = T * dp edge slots of a step
+  int H;           // slots of the owner table (traverse2_hash_slots)
+  size_t sq;       // float [qstride] the query
+  size_t qlds;     // u64 [qtot] the queues, or [TRV2_SB] the sort's staging block when they live in HBM
+  size_t newk;     // u64 [ecap] keys of this step, per worker segment
+  size_t eacc;     // over newk: int [ecap] row constant per edge slot (steps b-c; `newk` is written from step d on) ...
+  size_t wacc;     // over newk: int [ecap] ... and per entry of `work` (steps c-d0)
+  size_t sorted;   // u64 [ecap]
+  size_t wwk;      // over sorted, first half: u32 [ecap] worker of every entry of `work` (steps c-d0; `sorted` is written in step e)
+  size_t surv;     // over sorted, second half: u32 [ecap] ids that passed the 8-bit test (step d0)
+  size_t eid;      // u32 [ecap] neighbour id per edge slot
+  size_t eraw;     // u32 [ecap] 1 = this slot's test-and-set made the node visited
+  size_t work;     // u32 [ecap] ids to evaluate, per worker segment
+  size_t npos;     // int [ecap] insert positions
+  size_t hid;      // u32 [H] node id of the owner table, TRV2_NONE = empty
+  size_t hmin;     // int [H] lowest edge slot that met the node this step
+  size_t auxl;     // int [2 * Lq] MergeAll scratch (queues in LDS and T > 1)
+  size_t sh;       // int [trv2_sh_ints(T)]
+  Pf8Lds pf;       // prefilter only
+  size_t total;
+};
+// qglobal = queues in HBM
+EPS_GRAPH_HD inline Trv2Lds traverse2_lds(int dim, int T, int Lq, int64_t qtot, int dp, bool qglobal, bool prefilter, int cols8) {
+  Trv2Lds l;
+  l.H = traverse2_hash_slots(T, dp);
+  const size_t ecap = (size_t)T * dp, H = (size_t)l.H;
+  l.sq = 0;
+  l.qlds = l.sq + (size_t)lds_qstride(dim) * 4;
+  l.newk = l.qlds + (qglobal ? (size_t)TRV2_SB : (size_t)qtot) * 8;
+  l.eacc = l.newk;
+  l.wacc = l.eacc + ecap * 4;
+  l.sorted = l.newk + ecap * 8;
+  l.wwk = l.sorted;
+  l.surv = l.wwk + ecap * 4;
+  l.eid = l.sorted + ecap * 8;
+  l.eraw = l.eid + ecap * 4;
+  l.work = l.eraw + ecap * 4;
+  l.npos = l.work + ecap * 4;
+  l.hid = l.npos + ecap * 4;
+  l.hmin = l.hid + H * 4;
+  l.auxl = l.hmin + H * 4;
+  l.sh = l.auxl + ((qglobal || T == 1) ? 0 : (size_t)2 * Lq * 4);
+  const size_t end = l.sh + (size_t)trv2_sh_ints(T) * 4;
+  l.pf = pf8_lds(end, dim, cols8);
+  l.total = end + (prefilter ? l.pf.bytes : 0);
+  return l;
 }
+// LDS bytes of one workgroup
+EPS_GRAPH_HD inline size_t traverse2_lds_bytes(int dim, int T, int Lq, int64_t qtot, int dp, bool qglobal, bool prefilter = false, int cols8 = 0) {
+  return traverse2_lds(dim, T, Lq, qtot, dp, qglobal, prefilter, cols8).total;
+}
+
+// The 8-bit test pays only where it settles most neighbours: where more than 60 % of the neighbour evaluations still read the fp32 row
+// (distances small against the table's value range: clustered / low intrinsic dimension) it is pure overhead.  No evaluations: no verdict.
+inline bool prefilter_pays(double neighbour_evals, double fp32_rows_read) { return !(neighbour_evals > 0 && fp32_rows_read > 0.6 * neighbour_evals); }
 
 // ------------------------------------------------------------------------------------------------ launch plan of a traversal
 struct TrvIn {

@@ -371,7 +371,6 @@ static Trv2Args trv2_args(const TrvCall& c) {
   a.nbr = g.nbr.as<u32>();
   a.fixed_deg = g.fixed_deg;
   a.dp = pl.dp;
-  a.hslots = pl.hslots;
   a.init_ids = g.init_ids.as<u32>();
   a.L = (int)pl.L;
   a.Lq = (int)pl.Lq;
@@ -393,16 +392,8 @@ static Trv2Args trv2_args(const TrvCall& c) {
   a.elog = nullptr;
   a.elog_cnt = nullptr;
   a.elog_cap = (int)c.ecap;
-  a.x8 = c.prefilter ? c.q8v.x8 : nullptr;
-  a.acc0 = c.q8v.acc0;
+  a.p8 = prefilter8_args(c.q8v, c.prefilter, ix.dim_, c.vec4);
   a.nbr_acc0 = c.nbr_acc0;
-  a.scal8 = c.q8v.scal8;
-  a.d_pad8 = c.q8v.d_pad8;
-  a.cols8 = c.q8v.cols8;
-  a.u8 = c.q8v.u;
-  a.q8 = nullptr;
-  a.qstat8 = nullptr;
-  a.slack8 = prefilter_slack(ix.dim_, group_lanes(ix.dim_, c.vec4));
   return a;
 }
 
@@ -455,8 +446,8 @@ static int32_t run_slices(TrvCall& c, Trv2Args& a, PostArgs& pa) {
   for (int64_t q0 = 0; q0 < nq; q0 += slice) {
     const int64_t cnt = std::min(slice, nq - q0);
     a.queries = c.dq + q0 * ix.dim_;
-    a.q8 = c.prefilter ? g.q8.as<signed char>() + q0 * c.q8v.d_pad8 : nullptr;
-    a.qstat8 = c.prefilter ? g.qstat8.as<float>() + q0 * 4 : nullptr;
+    a.p8.q8 = c.prefilter ? g.q8.as<signed char>() + q0 * c.q8v.d_pad8 : nullptr;
+    a.p8.qstat8 = c.prefilter ? g.qstat8.as<float>() + q0 * 4 : nullptr;
     a.nq = cnt;
     a.out_queue = g.queue.as<u64>();
     if (c.filtered) {
@@ -507,13 +498,14 @@ static void print_profile(const TrvCall& c, const unsigned long long* h) {
   if (c.prefilter) fprintf(stderr, "[eps trv]   8-bit prefilter: %.1f of %.1f neighbour evaluations per query read the fp32 row\n", (double)h[4] / nq, (double)(h[0] - (unsigned long long)(L * nq)) / nq);
 }
 
-// The prefilter pays only where the 8-bit bound settles most neighbours (see GraphDev::pf_strikes): two consecutive searches in which more
-// than 60 % of the neighbour evaluations (h[0] less the seeds) still read the fp32 row (h[4]) switch it off for this graph.
+// The prefilter pays only where the 8-bit bound settles most neighbours (see GraphDev::pf_strikes): two consecutive searches in which it does
+// not (prefilter_pays, graph_host.hpp, over the neighbour evaluations - h[0] less the seeds - and the fp32 rows they read, h[4]) switch it off
+// for this graph.
 static void judge_prefilter(TrvCall& c, const unsigned long long* h) {
   const unsigned long long seeds = (unsigned long long)(c.pl.L * c.nq);
   const unsigned long long nbr_evals = h[0] > seeds ? h[0] - seeds : 0;
   if (nbr_evals < 4096) return;   // (not enough evaluations to judge)
-  c.g.pf_strikes = (double)h[4] > 0.6 * (double)nbr_evals ? c.g.pf_strikes + 1 : 0;
+  c.g.pf_strikes = prefilter_pays((double)nbr_evals, (double)h[4]) ? 0 : c.g.pf_strikes + 1;
   if (c.g.pf_strikes >= 2) c.g.pf_off = true;
 }
 

@@ -24,8 +24,7 @@
 //     is_visited.clear()/resize(n), :711-714, is O(N) per query; here it is O(evaluations)).  If the log
 //     overflows the slot's bitmap is cleared wholesale by the workgroup.
 #pragma once
-#include "graph_host.hpp"
-#include "kernels.hpp"
+#include "traverse_steps.hpp"
 
 namespace eps {
 
@@ -37,7 +36,6 @@ struct Trv2Args {
   const u32* nbr;       // CSR neighbours, or [n][fixed_deg] lists padded with 0xFFFFFFFF
   int fixed_deg;
   int dp;               // edge slots per worker and step (>= the longest adjacency list)
-  int hslots;           // slots of the per-step ownership table: power of two >= 2*T*dp, 0 when T == 1
   const u32* init_ids;  // [L]
   const float* queries;
   int64_t nq;
@@ -65,22 +63,12 @@ struct Trv2Args {
   u64* elog;                     // [nq][elog_cap] or null
   u32* elog_cnt;                 // [nq] evaluations of the query (may exceed elog_cap: only the first elog_cap are stored)
   int elog_cap;
-  // exact lower-bound prefilter of step d on the table's 8-bit mirror (mirror_build.hip: one grid per table, integer dot product,
-  // the row constant folded into acc0): a neighbour whose 768-byte mirror row PROVES `dist > bound` is dropped without its fp32
-  // row ever being read; every other neighbour goes through the unchanged fp32 evaluation.  Results are bit-identical with or
-  // without it (the proof is the flat engine's: device_common.hpp stage_threshold8).  x8 == null: off.
-  const signed char* x8;         // [n_pad][d_pad8]
-  const int* acc0;               // [n_pad]
+  // exact lower-bound prefilter of step d (traverse_steps.hpp)
+  Prefilter8Args p8;
   // r5: the row constants of a node's neighbours stored WITH its adjacency list ([n][fixed_deg], same layout as nbr): an expansion reads them
   // in the same access as the list, and the prefilter finds them in LDS instead of gathering 4 scattered bytes per evaluation (what bounds
   // the kernel is the number of scattered locations per evaluation, profiles/r5_traverse_lab_10M_proxy.txt).  null: gather acc0[id].
   const int* nbr_acc0;
-  const float* scal8;            // the mirror's table-wide bounds (residual, |xh|, |x|^2, -, |R|)
-  const signed char* q8;         // [nq][d_pad8] the queries on the same grid
-  const float* qstat8;           // [nq][4] |q|^2, |q|, |q - qh|, C + c
-  int d_pad8;
-  int cols8;                     // leading bytes of a mirror row that carry values (Quant8View::cols8: dim, or dim rounded up to 256 in the rotated frame)
-  float u8, slack8;
 };
 
 constexpr int TRV2_U = 4;     // rows in flight per lane group in the distance phases
@@ -88,10 +76,8 @@ constexpr int TRV2_UPF = 3;   // prefilter form of the kernel: fp32 rows in flig
 constexpr int TRV2_NL = 3;    // ... and 16-byte pieces of each (row_dists, device_common.hpp).  r5: 3 x 3 (4 x 1 until r4; profiles/r5_traverse_lab_10M_proxy.txt)
 constexpr int TRV2_U8 = 3;    // prefilter: mirror rows in flight per lane group (2 until r4) ...
 constexpr int TRV2_NL8 = 3;   // ... and 16-byte pieces of each per lane
-// TRV2_SB, TRV2_MAXT and the sizes of the LDS arrays below (trv2_*, traverse2_hash_slots, traverse2_lds_bytes): graph_host.hpp
+// TRV2_SB, TRV2_MAXT, the kernel's LDS layout (Trv2Lds) and the slots of its scalar scratch (Trv2Slot): graph_host.hpp
 constexpr u32 TRV2_NONE = 0xFFFFFFFFu;
-
-__device__ __forceinline__ u64 q2key(float d, u32 id) { return ((u64)f2ord(d + 0.0f) << 32) | ((u64)id << 1); }
 
 // number of keys in q[0..n) ordered before x (both compared without the checked bit)
 __device__ __forceinline__ int lower_bound_q(const u64* q, int n, u64 x) {
@@ -104,25 +90,6 @@ __device__ __forceinline__ int lower_bound_q(const u64* q, int n, u64 x) {
   return lo;
 }
 
-// compare-exchange network passes of a bitonic sort over buf[0..n) (n a power of two) for strides
-// stride_hi, stride_hi/2, ..., 1; `gbase` is the global index of buf[0], `size` the bitonic block size.
-template <int NT>
-__device__ __forceinline__ void bitonic_passes(u64* buf, int n, int64_t gbase, int64_t size, int stride_hi) {
-  for (int stride = stride_hi; stride > 0; stride >>= 1) {
-    for (int i = threadIdx.x; i < (n >> 1); i += NT) {
-      const int lo = ((i / stride) * (stride << 1)) + (i % stride);
-      const int hi = lo + stride;
-      const bool up = (((gbase + lo) & size) == 0);
-      const u64 x = buf[lo], y = buf[hi];
-      if ((x > y) == up) {
-        buf[lo] = y;
-        buf[hi] = x;
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // PF: with the 8-bit prefilter (step d0).  Compiled for 4 wavefronts per SIMD (<= 128 VGPRs, the occupancy the host side plans
 // with; a handful of dwords spill outside the loops); the form without it needs no such cap (109-117 VGPRs, nothing spilled).
 template <bool VEC4, int NW, bool QGLOBAL, bool PF>
@@ -132,28 +99,26 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
   constexpr int C = NT * R;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int dim = a.dim;
-  const int qstride = (dim + 3) & ~3;
+  const int qstride = lds_qstride(dim);
   const int T = a.T, L = a.L, Lq = a.Lq, DP = a.dp;
-  const int ecap = T * DP;
-  float* sq = reinterpret_cast<float*>(smem_raw);                          // [qstride]
-  u64* qlds = reinterpret_cast<u64*>(sq + qstride);                         // queues (or the sort staging block)
-  u64* newk = qlds + (QGLOBAL ? (int64_t)TRV2_SB : a.qtot);                 // [ecap] keys of this step, per worker segment
-  u64* sorted = newk + ecap;                                                // [ecap]
-  u32* eid = reinterpret_cast<u32*>(sorted + ecap);                         // [ecap] neighbour id per edge slot
-  u32* eraw = eid + ecap;                                                   // [ecap] 1 = this slot's atomicOr set the bit
-  u32* work = eraw + ecap;                                                  // [ecap] ids to evaluate, per worker segment
-  int* npos = reinterpret_cast<int*>(work + ecap);                          // [ecap] insert positions
-  int* eacc = reinterpret_cast<int*>(newk);                                 // PF, nbr_acc0: [ecap] row constant per edge slot (steps b-c; `newk` is written from step d on)
-  int* wacc = eacc + ecap;                                                  //               [ecap] ... per entry of `work` (steps c-d0)
-  u32* wwk = reinterpret_cast<u32*>(sorted);                                // PF: [ecap] worker of every entry of `work` (steps c-d0; `sorted` is written in step e)
-  const int H = a.hslots;                                                   // ownership table slots (power of two; 0 when T == 1)
-  u32* hid = reinterpret_cast<u32*>(npos + ecap);                           // [H] node id, TRV2_NONE = empty
-  int* hmin = reinterpret_cast<int*>(hid + H);                              // [H] lowest edge slot that met the node this step
-  int* auxl = hmin + H;                                                     // !QGLOBAL: [2*Lq] MergeAll scratch (T > 1)
-  int* sh = auxl + ((QGLOBAL || T == 1) ? 0 : 2 * Lq);                      // [trv2_sh_ints(T)]
-  // sh[0] scratch (first found / pmin), sh[1] unchecked count, sh[2] undo-log fill, sh[3] any worker selected,
-  // sh[4] running prefix, sh[5] non-duplicate count, sh[6] r of MergeAll, sh[7] log overflow, sh[8] evaluations logged (elog),
-  // sh[9] prefilter threshold of this step
+  const Trv2Lds l = traverse2_lds(dim, T, Lq, a.qtot, DP, QGLOBAL, PF, a.p8.cols8);
+  float* sq = reinterpret_cast<float*>(smem_raw + l.sq);
+  u64* qlds = reinterpret_cast<u64*>(smem_raw + l.qlds);
+  u64* newk = reinterpret_cast<u64*>(smem_raw + l.newk);
+  int* eacc = reinterpret_cast<int*>(smem_raw + l.eacc);   // (PF, nbr_acc0)
+  int* wacc = reinterpret_cast<int*>(smem_raw + l.wacc);
+  u64* sorted = reinterpret_cast<u64*>(smem_raw + l.sorted);
+  u32* wwk = reinterpret_cast<u32*>(smem_raw + l.wwk);     // (PF)
+  u32* surv = reinterpret_cast<u32*>(smem_raw + l.surv);
+  u32* eid = reinterpret_cast<u32*>(smem_raw + l.eid);
+  u32* eraw = reinterpret_cast<u32*>(smem_raw + l.eraw);
+  u32* work = reinterpret_cast<u32*>(smem_raw + l.work);
+  int* npos = reinterpret_cast<int*>(smem_raw + l.npos);
+  const int H = l.H;                                       // slots of the owner table, 0 when T == 1
+  u32* hid = reinterpret_cast<u32*>(smem_raw + l.hid);
+  int* hmin = reinterpret_cast<int*>(smem_raw + l.hmin);
+  int* auxl = reinterpret_cast<int*>(smem_raw + l.auxl);
+  int* sh = reinterpret_cast<int*>(smem_raw + l.sh);
   const int TS = trv2_tstride(T);
   const int SH = trv2_sh_ints(T);
   int* s_kuc = sh + 16;            // [T] first possibly-unchecked position per queue
@@ -167,15 +132,12 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
   int* s_selpos = s_wave + 16;     // [T] queue position of the selected candidate
   int* s_pcnt = s_selpos + TS;     // [T] ids that passed the 8-bit prefilter
   int* s_eoff = s_pcnt + TS;       // [T+1] first edge slot of every worker in this step
-  // prefilter block (only present in the launch's LDS size when a.x8): statistics of the query on the table's grid, then the query
-  constexpr bool pf = PF;   // (a.x8 != null)
-  const size_t pf_off = ((size_t)(reinterpret_cast<unsigned char*>(sh + SH) - smem_raw) + 15) & ~(size_t)15;
-  float* qst = reinterpret_cast<float*>(smem_raw + pf_off);                // [4] |q|^2, |q|, |q - qh|, C + c
-  signed char* sq8 = reinterpret_cast<signed char*>(qst + 4);               // [q8len]
-  const int q8len = trv2_q8len(a.cols8 > dim ? a.cols8 : dim);
+  constexpr bool pf = PF;   // (a.p8.x8 != null)
+  float* qst = reinterpret_cast<float*>(smem_raw + l.pf.qst);
+  signed char* sq8 = reinterpret_cast<signed char*>(smem_raw + l.pf.sq8);
+  const int q8len = q8_bytes(dim, a.p8.cols8);
   constexpr int U8 = TRV2_U8, NL8 = TRV2_NL8;
-  int G8 = 4;
-  while (G8 < 64 && G8 * 16 * NL8 < q8len) G8 <<= 1;                        // lanes per mirror row (NL8 pieces of 16 bytes each)
+  const int G8 = lanes_per_row8(q8len, NL8);
   const int RPW8 = 64 / G8;
 
   const int tid = threadIdx.x;
@@ -208,11 +170,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
 
   for (int64_t q = slot; q < a.nq; q += gridDim.x) {
     // ------------------------------------------------------------------ InitializeSetLPara (:446-485)
-    for (int i = tid; i < qstride; i += NT) sq[i] = i < dim ? a.queries[q * dim + i] : 0.f;
-    if (pf) {   // the query on the table's grid and its statistics (query_prep8_kernel, launched ahead of this kernel)
-      for (int i = tid; i < (q8len >> 2); i += NT) reinterpret_cast<u32*>(sq8)[i] = reinterpret_cast<const u32*>(a.q8 + q * a.d_pad8)[i];
-      if (tid < 4) qst[tid] = a.qstat8[q * 4 + tid];
-    }
+    stage_query<NT>(a.queries, q, dim, qstride, sq, pf, a.p8, q8len, sq8, qst);
     for (int i = tid; i < SH; i += NT) sh[i] = 0;
     for (int i = tid; i < H; i += NT) {
       hid[i] = TRV2_NONE;
@@ -242,9 +200,9 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
       for (int u = 0; u < U; ++u)
         if (ok[u] && t == 0) {
           const float dseed = finish_dist(a.metric, acc[u][0]);
-          master[c0 + u * RPW + g] = q2key(dseed, id[u]);
+          master[c0 + u * RPW + g] = qkey(dseed, id[u]);
           if (a.elog) {
-            const int lp = atomicAdd(&sh[8], 1);
+            const int lp = atomicAdd(&sh[TRV2_ELOG], 1);
             if (lp < a.elog_cap) a.elog[q * (int64_t)a.elog_cap + lp] = make_key(dseed, id[u]);
           }
         }
@@ -300,7 +258,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
         // when worker 0's queue is full, i.e. after unchecked candidate number (Lq-1)*T.
         const int kmaster = s_kuc[T - 1];
         const int imax = (Lq - 1) * T;
-        if (tid == 0) sh[4] = 0;
+        if (tid == 0) sh[TRV2_PREFIX] = 0;
         __syncthreads();
         for (int base = kmaster; base < L; base += NT) {
           const int p = base + tid;
@@ -308,7 +266,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           const u64 m = __ballot(un);
           if (lane == 0) s_wave[wave] = __popcll(m);
           __syncthreads();
-          int i = sh[4];
+          int i = sh[TRV2_PREFIX];
           for (int w2 = 0; w2 < wave; ++w2) i += s_wave[w2];
           i += __popcll(m & ((1ull << lane) - 1ull));
           if (un && i <= imax) {
@@ -320,13 +278,13 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           }
           __syncthreads();
           if (tid == 0) {
-            int tot = sh[4];
+            int tot = sh[TRV2_PREFIX];
             for (int w2 = 0; w2 < NW; ++w2) tot += s_wave[w2];
-            sh[4] = tot;
+            sh[TRV2_PREFIX] = tot;
           }
           __syncthreads();
         }
-        const int U_ = sh[4];   // unchecked candidates seen
+        const int U_ = sh[TRV2_PREFIX];   // unchecked candidates seen
         if (U_ == 0) break;     // uniform: no unchecked candidate left -> the search is over (:609-611)
         if (tid < T) {
           const int last = (U_ - 1 < imax) ? U_ - 1 : imax;   // highest unchecked index that was distributed
@@ -344,7 +302,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
       while (true) {
         // a. every worker with iterations left takes its first unchecked candidate at or after k_uc (:632-672).  One
         //    wavefront per worker (ballot over 64 queue positions at a time), the workers side by side.
-        // (sh[3] "somebody selected" and sh[10] "nodes to evaluate" are zero here: zeroed with the query's scratch, and again at the end of every step -
+        // (sh[TRV2_ANYSEL] "somebody selected" and sh[TRV2_NEVAL] "nodes to evaluate" are zero here: zeroed with the query's scratch, and again at the end of every step -
         // r5: a barrier of this workgroup costs ~0.4 us among 16 wavefronts per CU, a step had 17 of them, a T = 1 step lasts 17 us)
         for (int w = wave; w < T; w += NW) {
           u64* qw = qbase + (int64_t)w * Lq;
@@ -371,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
               s_kuc[w] = found;
               s_its[w] += 1;
               s_deg[w] = a.fixed_deg > 0 ? a.fixed_deg : (int)(a.off[node + 1] - a.off[node]);
-              sh[3] = 1;
+              sh[TRV2_ANYSEL] = 1;
             } else {
               s_sel[w] = -1;
               s_deg[w] = 0;
@@ -398,7 +356,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           __syncthreads();
         }
         TRV2_LAP(2)
-        if (!sh[3]) break;   // uniform: nobody expanded -> the round is over
+        if (!sh[TRV2_ANYSEL]) break;   // uniform: nobody expanded -> the round is over
         ++steps;
         const float bound = key_dist(master[L - 1]);   // last_dist (:546): worst of the master queue before this step
 
@@ -464,7 +422,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
             if (PF) {
               // prefilter form (r5): ONE list of the step's nodes to evaluate, whatever worker they belong to - the mirror-row passes index it
               // directly (they used to map every item to (worker, offset) through the per-worker counts: T - 1 dependent LDS reads per row)
-              const int pos = atomicAdd(&sh[10], 1);
+              const int pos = atomicAdd(&sh[TRV2_NEVAL], 1);
               work[pos] = nb;
               wwk[pos] = (u32)w;
               if (a.nbr_acc0) wacc[pos] = eacc[e];
@@ -473,13 +431,13 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
               work[s_eoff[w] + pos] = nb;
             }
             if (!gen) {
-              const int ls = atomicAdd(&sh[2], 1);
-              if (ls < a.vcap) vlog[ls] = nb; else sh[7] = 1;
+              const int ls = atomicAdd(&sh[TRV2_VLOG], 1);
+              if (ls < a.vcap) vlog[ls] = nb; else sh[TRV2_VLOG_OVER] = 1;
             }
           }
         }
         if (pf) {   // (step d0's threshold and survivor counters: laid down here, under this step's barrier)
-          if (tid == 0) sh[9] = stage_threshold8(bound, qst, a.scal8, a.metric, a.u8, a.slack8, 0);
+          if (tid == 0) sh[TRV2_TQ] = stage_threshold8(bound, qst, a.p8.scal8, a.metric, a.p8.u8, a.p8.slack8, 0);
           if (tid < T) s_pcnt[tid] = 0;
         }
         __syncthreads();
@@ -492,7 +450,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
         // d. distances of all surviving neighbours (every wavefront, 16 B/lane row loads); candidates beyond the
         //    bound are dropped (`dist > dist_bound`, :427)
         int nwork = 0;
-        if (PF) nwork = sh[10];
+        if (PF) nwork = sh[TRV2_NEVAL];
         else
           for (int w = 0; w < T; ++w) nwork += s_wcnt[w];
         evals += nwork;
@@ -502,11 +460,8 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           // d0. 8-bit lower bound first: dot(xi, qi) + acc0[x] >= Tq(bound) is NECESSARY for dist <= bound (the integer dot product is
           //     exact, the row constant and the quantisation residuals are on the safe side of the threshold), so only the rows that
           //     pass are worth their 4 d bytes.  Survivors are compacted per worker; everything downstream sees the smaller lists.
-          const int Tq = sh[9];
-          u32* surv = reinterpret_cast<u32*>(sorted) + ecap;   // (the second half of `sorted`: written in step e only)
+          const int Tq = sh[TRV2_TQ];
           const int g8 = lane / G8, t8 = lane & (G8 - 1);
-          // G8 lanes per row, every lane NL8 16-byte pieces of it 16*G8 bytes apart (one instruction covers 16*G8 contiguous bytes
-          // of each of its 64/G8 rows); U8 rows per lane group: U8*NL8 loads in flight per lane, 64/G8*U8 rows per wavefront and pass
           for (int c0 = wave * RPW8 * U8; c0 < nwork; c0 += NW * RPW8 * U8) {
             const signed char* rp8[U8];
             int wslot[U8], dot[U8], a0[U8];   // wslot: (worker << 16) | slot of the id in `work`, -1 = past the end
@@ -518,42 +473,10 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
               const int sl = ci;
               wslot[u] = ok ? sl : -1;
               const u32 id = work[sl];
-              rp8[u] = a.x8 + (int64_t)id * a.d_pad8;
-              a0[u] = t8 == 0 ? (a.nbr_acc0 ? wacc[sl] : a.acc0[id]) : 0;    // (gathered: in flight with the row pieces)
-              dot[u] = 0;
+              rp8[u] = a.p8.x8 + (int64_t)id * a.p8.d_pad8;
+              a0[u] = t8 == 0 ? (a.nbr_acc0 ? wacc[sl] : a.p8.acc0[id]) : 0;    // (gathered: in flight with the row pieces)
             }
-#pragma unroll 1
-            for (int c = t8 * 16; c < q8len; c += G8 * 16 * NL8) {
-              i32x4 xv[U8][NL8];
-#pragma unroll
-              for (int j = 0; j < NL8; ++j) {
-                const int cj = c + j * G8 * 16;
-                const bool in = cj < q8len;
-#pragma unroll
-                for (int u = 0; u < U8; ++u) xv[u][j] = in ? *reinterpret_cast<const i32x4*>(rp8[u] + cj) : i32x4{0, 0, 0, 0};
-              }
-#pragma unroll
-              for (int j = 0; j < NL8; ++j) {
-                const int cj = c + j * G8 * 16;
-                const i32x4 qv = cj < q8len ? *reinterpret_cast<const i32x4*>(sq8 + cj) : i32x4{0, 0, 0, 0};
-#pragma unroll
-                for (int u = 0; u < U8; ++u) {
-                  dot[u] = __builtin_amdgcn_sdot4(xv[u][j][0], qv[0], dot[u], false);
-                  dot[u] = __builtin_amdgcn_sdot4(xv[u][j][1], qv[1], dot[u], false);
-                  dot[u] = __builtin_amdgcn_sdot4(xv[u][j][2], qv[2], dot[u], false);
-                  dot[u] = __builtin_amdgcn_sdot4(xv[u][j][3], qv[3], dot[u], false);
-                }
-              }
-            }
-            if (G8 == 16) {   // (one DPP row per mirror row - d in (512, 768]: 4 VALU instructions per sum instead of 4 LDS-crossbar round trips; integer sums, any order)
-#pragma unroll
-              for (int u = 0; u < U8; ++u) dot[u] = row16_sum(dot[u]);
-            } else {
-              for (int o = G8 >> 1; o > 0; o >>= 1) {
-#pragma unroll
-                for (int u = 0; u < U8; ++u) dot[u] += __shfl_xor(dot[u], o);
-              }
-            }
+            mirror_dots<U8, NL8>(rp8, sq8, q8len, G8, t8, dot);
 #pragma unroll
             for (int u = 0; u < U8; ++u)
               if (wslot[u] >= 0 && t8 == 0 && dot[u] + a0[u] >= Tq) {
@@ -599,9 +522,9 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           for (int u = 0; u < U; ++u) {
             if (ok[u] && t == 0) {
               const float d = finish_dist(a.metric, acc[u][0]);
-              newk[slotk[u]] = (d > bound) ? KEY_EMPTY : q2key(d, id[u]);
+              newk[slotk[u]] = (d > bound) ? KEY_EMPTY : qkey(d, id[u]);
               if (a.elog) {   // (also the candidates the bound drops: a visible row beyond the queue's worst may still be an answer)
-                const int lp = atomicAdd(&sh[8], 1);
+                const int lp = atomicAdd(&sh[TRV2_ELOG], 1);
                 if (lp < a.elog_cap) a.elog[q * (int64_t)a.elog_cap + lp] = make_key(d, id[u]);
               }
             }
@@ -661,7 +584,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           const u64* sw = sorted + (w < T ? s_eoff[w] : 0);
           int* np = npos + (w < T ? s_eoff[w] : 0);
           for (int j = tg; j < nnew; j += TPW) np[j] = j + lower_bound_q(qw, size, sw[j]);
-          if (tid == 0) sh[0] = 0;
+          if (tid == 0) sh[TRV2_SCRATCH] = 0;
           __syncthreads();
           const int pmin = nnew > 0 ? np[0] : cap;
           const bool moves = nnew > 0 && pmin < cap && size > 0;
@@ -669,9 +592,9 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
           const int nchunks = moves ? (top / CW - pmin / CW + 1) : 0;
           int maxchunks = 1;
           if (L > CW || Lq > CW) {   // (queues longer than one chunk per worker: the workers agree on the trip count; else one predicated trip)
-            if (tg == 0 && nchunks > 0) atomicMax(&sh[0], nchunks);
+            if (tg == 0 && nchunks > 0) atomicMax(&sh[TRV2_SCRATCH], nchunks);
             __syncthreads();
-            maxchunks = sh[0];
+            maxchunks = sh[TRV2_SCRATCH];
           }
           // old entries at positions >= pmin move right by the number of new keys ordered before them; chunks from the tail so
           // that nothing unread is overwritten
@@ -705,8 +628,8 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
             s_kuc[w] = r <= kuc ? r : kuc + 1;   // (:661-665)
           }
           if (tid == 0) {   // (for the next step's select, see there)
-            sh[3] = 0;
-            sh[10] = 0;
+            sh[TRV2_ANYSEL] = 0;
+            sh[TRV2_NEVAL] = 0;
           }
           __syncthreads();
         }
@@ -734,7 +657,7 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
         const int r = bpos[0] & 0x7FFFFFFF;   // lowest insert position (lower_bound of the worker's best key, :158-163)
         if (r < L) {
           // pass 2: ndp[j] = non-duplicate worker keys before j
-          if (tid == 0) sh[4] = 0;
+          if (tid == 0) sh[TRV2_PREFIX] = 0;
           __syncthreads();
           for (int base = 0; base < nb; base += NT) {
             const int j = base + tid;
@@ -742,19 +665,19 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
             const u64 m = __ballot(nd);
             if (lane == 0) s_wave[wave] = __popcll(m);
             __syncthreads();
-            int i = sh[4];
+            int i = sh[TRV2_PREFIX];
             for (int w2 = 0; w2 < wave; ++w2) i += s_wave[w2];
             i += __popcll(m & ((1ull << lane) - 1ull));
             if (j < nb) ndp[j] = i;
             __syncthreads();
             if (tid == 0) {
-              int tot = sh[4];
+              int tot = sh[TRV2_PREFIX];
               for (int w2 = 0; w2 < NW; ++w2) tot += s_wave[w2];
-              sh[4] = tot;
+              sh[TRV2_PREFIX] = tot;
             }
             __syncthreads();
           }
-          const int nnd = sh[4];
+          const int nnd = sh[TRV2_PREFIX];
           // pass 3: master entries at positions >= r move right by the non-duplicate worker keys ordered before them
           for (int cb = ((L - 1) / C) * C; cb + C > r && cb >= 0; cb -= C) {
             u64 v[R];
@@ -799,16 +722,16 @@ __global__ __launch_bounds__(NW * 64, PF ? 4 : 1) void traverse2_kernel(Trv2Args
     if (a.out_queue)
       for (int i = tid; i < L; i += NT) a.out_queue[q * L + i] = master[i];
     if (a.elog_cnt && tid == 0) {
-      a.elog_cnt[q] = (u32)sh[8];
-      if ((int)sh[8] > a.elog_cap) {   // the log was too short for this walk: the host repeats the search with a longer one
+      a.elog_cnt[q] = (u32)sh[TRV2_ELOG];
+      if ((int)sh[TRV2_ELOG] > a.elog_cap) {   // the log was too short for this walk: the host repeats the search with a longer one
         atomicAdd(&a.counters[5], 1ull);
-        atomicMax(&a.counters[6], (unsigned long long)sh[8]);
+        atomicMax(&a.counters[6], (unsigned long long)sh[TRV2_ELOG]);
       }
     }
-    const int nlog = sh[2];
+    const int nlog = sh[TRV2_VLOG];
     if (gen) {
       // (nothing to undo: the next query of this slot carries a larger stamp)
-    } else if (sh[7] || nlog > a.vcap) {
+    } else if (sh[TRV2_VLOG_OVER] || nlog > a.vcap) {
       for (int64_t i = tid; i < a.words; i += NT) vis[i] = 0;
     } else {
       for (int i = tid; i < L; i += NT) vis[a.init_ids[i] >> 5] = 0;
