@@ -28,6 +28,8 @@
  *   eps_index_search_among          the row-by-row loops in which SearchByAttribute judges a primary-key list or a geo index's id list
  *                                   (db/execution/vec_search_executor.cpp:966-1013), with a distance and a top-k on top: the k closest
  *                                   of the rows the CALLER names - the allow-list search, the second stage of a hybrid search
+ *   eps_index_search_groups         (new) the k closest groups of rows, each by its closest row; the reference's relative is the host-side
+ *                                   grouping of a finished answer (FacetExecutor, db/execution/aggregation.hpp) - it has no grouped search
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
  *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
@@ -468,6 +470,43 @@ int32_t eps_index_search_range(eps_index* h, const float* queries, int64_t nq, c
  * search can observe changes. */
 int32_t eps_index_search_among(eps_index* h, const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand,
                                int32_t k, int64_t* ids_out, float* dist_out, int32_t* counts_out);
+/* Grouped search: the k closest GROUPS of rows per query, each represented by its closest row - the call behind "the k best documents" over a
+ * table of chunks.  The reference has no such call: it groups answers by an attribute on the host after the search (FacetExecutor,
+ * db/execution/aggregation.hpp), and a caller of eps_index_search has to over-fetch, drop repeats on the host and search again.
+ * eps_index_set_groups gives every row one int64 key: keys is a host or device int64[n], n must equal eps_index_row_count (else EPS_USER_ERROR);
+ * any value is a key (negative, INT64_MIN, INT64_MAX, non-contiguous); rows with equal keys form a group.  The library relabels the keys to dense
+ * int32 labels on the host (sort, unique, binary search: a set-up step) and keeps label[n] and key_of_label[G] on the device.  keys == NULL
+ * forgets the groups.  After eps_index_attach_rows / eps_index_append_rows the labels are stale: eps_index_search_groups returns EPS_USER_ERROR
+ * until the keys are set again, the rule a stale bitset follows.
+ * The rule, for query j.  V_j = the rows of [0, eps_index_row_count) that are visible exactly as for eps_index_search_among: not deleted, passing
+ * the int-column test and the installed program, `@distance` reading the row's exact distance.  The distance of (row, query) is, bit for bit,
+ * the value eps_index_search in EPS_MODE_FLAT returns for that pair.  Every group with a row in V_j is represented by its row of V_j with the
+ * smallest (distance, row) key - ties to the smaller row, a NaN distance after +inf, a group whose only visible rows are NaN still a group - and
+ * the answer is the k smallest representatives in ascending key order.  Equivalently: walk V_j in ascending key order, keep a row iff its group
+ * has not been seen, stop at k.  ids_out [nq][k] (through eps_index_set_id_map), dist_out [nq][k], group_keys_out [nq][k] (the caller's key of
+ * each kept row), counts_out [nq] (may be NULL) = min(k, groups with a row in V_j); the unused slots -1 / +inf / key 0 (the count says which
+ * slots are used).  queries and the outputs: host or device, the outputs all of one kind - device: on the index's stream, the caller
+ * synchronises; host: the call synchronises.  1 <= k <= 1024; nq = 0: EPS_OK; no groups set: EPS_USER_ERROR.  p: only flat_engine is read (NULL:
+ * defaults).  engine: EPS_GROUPS_PAGES takes the keys in ascending order a page of page_rows at a time - the first page from the flat engine a
+ * search of (nq, page_rows) would use, later pages from the stream scan's continuation, only for the queries still unfinished - and keeps the
+ * first occurrence of every label (csrc/groups.hip); a query is finished when it holds k representatives or its page came back short; one host
+ * sync per round.  EPS_GROUPS_SCAN streams the table once per 4 queries and takes the minimum key per (query, group) with 64-bit atomics into a
+ * table of c x G x 8 bytes, c queries at a time (c a multiple of 4 derived from scratch_bytes, never below 4), then reads the k smallest slots
+ * back.  EPS_GROUPS_AUTO runs one round of pages and gives exactly the queries still unfinished to the scan: a table whose close rows are
+ * spread over many groups is answered by the page, one whose close rows belong to few groups costs one scan instead of n / page_rows pages.
+ * All three return the same bits.  page_rows: 0 = min(1024, 4 k rounded up to 64), or 1..1024.  scratch_bytes: 0 = 256 MiB, or a cap on the
+ * scan's table; a failed allocation: EPS_INFRA_UNEXPECTED_ERROR.  eps_index_last_stats reports the call like a search.
+ * eps_index_groups_info: *n_groups = G, *largest_group = rows of the largest group (both 0 while no groups are set), *last_engines = a mask of
+ * (1 << EPS_GROUPS_PAGES) | (1 << EPS_GROUPS_SCAN) over the engines the last eps_index_search_groups ran, *last_scan_queries = how many of its
+ * queries the scan answered; any pointer may be NULL.  A sharded handle: EPS_DB_UNSUPPORTED_ERROR from all three.  Nothing a later search
+ * can observe changes. */
+#define EPS_GROUPS_AUTO 0
+#define EPS_GROUPS_PAGES 1
+#define EPS_GROUPS_SCAN 2
+int32_t eps_index_set_groups(eps_index* h, const int64_t* keys, int64_t n);
+int32_t eps_index_search_groups(eps_index* h, const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                                int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out);
+int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

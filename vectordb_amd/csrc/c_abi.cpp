@@ -267,6 +267,14 @@ int32_t eps_index_search_among(eps_index* h, const float* q, int64_t nq, const i
   return on_single_device(h, "search_among: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
                           [&](Index& ix) { return ix.search_among(q, nq, cand_ids, cand_offsets, n_cand, k, ids, dist, counts); });
 }
+int32_t eps_index_set_groups(eps_index* h, const int64_t* keys, int64_t n) { GUARD(h, IX(h)->set_groups(keys, n)); }
+int32_t eps_index_search_groups(eps_index* h, const float* q, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                                int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* counts) {
+  GUARD(h, IX(h)->search_groups(q, nq, k, p, engine, page_rows, scratch_bytes, ids, dist, group_keys, counts));
+}
+int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) {
+  GUARD(h, IX(h)->groups_info(n_groups, largest_group, last_engines, last_scan_queries));
+}
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;
   return const_cast<IndexBase*>(CIX(h))->last_stats(out);

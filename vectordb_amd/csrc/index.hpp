@@ -116,6 +116,11 @@ class IndexBase {
   virtual int32_t load_graph(const char* path) = 0;
   virtual int32_t search(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int64_t* ids, float* dist,
                          int32_t* counts, int32_t walk_limit = 0) = 0;
+  // the grouped search (eps_index_set_groups / _search_groups / _groups_info; groups.hip): a single-device index serves it, a shard group refuses
+  virtual int32_t set_groups(const int64_t* keys, int64_t n) = 0;
+  virtual int32_t search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                                int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out) = 0;
+  virtual int32_t groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) = 0;
   virtual int64_t row_count() const = 0;
   virtual int32_t last_stats(eps_search_stats* out) = 0;
   virtual int kernel_times(double* ms_out, int cap) = 0;
@@ -175,6 +180,12 @@ class Index : public IndexBase {
   // the k closest visible rows among the ids the caller names: one list for the batch, or one per query (eps_index_search_among; among.hip)
   int32_t search_among(const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k,
                        int64_t* ids_out, float* dist_out, int32_t* counts_out);
+
+  // the k closest groups of rows, each by its closest visible row (eps_index_search_groups; groups.hip, plan: groups_host.hpp)
+  int32_t set_groups(const int64_t* keys, int64_t n) override;
+  int32_t search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows, int64_t scratch_bytes,
+                        int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out) override;
+  int32_t groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) override;
 
   int64_t row_count() const override { return n_rows_; }
 
@@ -245,6 +256,13 @@ class Index : public IndexBase {
   // last_stats once the call's last event has passed (among_evals_pending_), so that a call with device results stays asynchronous
   DevBuf among_in_;
   bool among_evals_pending_ = false;
+  // set_groups(): label[n] | key_of_label[G], valid for the table of (grp_version_, grp_rows_).  search_groups(): a page of keys [nq][P]; the
+  // result keys [nq][k]; [lo | compacted lo | counts | status | query numbers]; the compacted queries; the scan's table, its merged lists and
+  // [ids | group keys | distances | counts] of a call with host result pointers.  h_grp_: the word the compaction leaves the host
+  DevBuf grp_label_, grp_keys_, grp_page_, grp_res_, grp_state_, grp_q_, grp_table_, grp_run_, grp_out_;
+  HostBuf h_grp_;
+  int64_t grp_n_groups_ = 0, grp_largest_ = 0, grp_rows_ = -1, grp_version_ = -1, grp_last_scan_queries_ = 0;
+  int32_t grp_last_engines_ = 0;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   // main-kernel event pairs of the last KRING search calls (read back after a run without a sync inside it);
   // evk0_/evk1_ alias the pair of the call in progress

@@ -1,4 +1,4 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, the steps they share, and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, the steps they share, and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
@@ -569,6 +569,194 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {
     rc = fetch_to_host(d_ids, out_bytes, {{ids, 0, ids_bytes}, {dist, ids_bytes, dist_bytes}, {counts, ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ set_groups, search_groups
+// One int64 key per row -> dense labels (groups_relabel, on the host: a set-up step) kept on the device next to the keys they stand for.
+int32_t Index::set_groups(const int64_t* keys, int64_t n) {
+  HIP_TRY(hipSetDevice(device_));
+  HIP_TRY(hipStreamSynchronize(stream_));   // (a call in flight may read the labels this one replaces)
+  grp_rows_ = -1;   // forgotten, also where the call fails below
+  grp_n_groups_ = grp_largest_ = 0;
+  if (!keys) return EPS_OK;
+  if (n != n_rows_) return fail(EPS_USER_ERROR, "set_groups: n must equal the table's row count");
+  std::vector<int64_t> from_device, key_of_label;
+  std::vector<int32_t> label((size_t)n);
+  if (n > 0 && is_device_ptr(keys)) {
+    from_device.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(from_device.data(), keys, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    keys = from_device.data();
+  }
+  int64_t largest = 0;
+  const int64_t G = groups_relabel(keys, n, label.data(), &key_of_label, &largest);
+  if (n > 0) {
+    if (!grp_label_.reserve((size_t)n * sizeof(int32_t)) || !grp_keys_.reserve((size_t)G * sizeof(int64_t)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "set_groups: out of device memory");
+    HIP_TRY(hipMemcpyAsync(grp_label_.p, label.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(grp_keys_.p, key_of_label.data(), (size_t)G * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));   // (the vectors end with this call)
+  }
+  grp_n_groups_ = G;
+  grp_largest_ = largest;
+  grp_rows_ = n;
+  grp_version_ = rows_version_;
+  return EPS_OK;
+}
+
+int32_t Index::groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) {
+  if (n_groups) *n_groups = grp_rows_ >= 0 ? grp_n_groups_ : 0;
+  if (largest_group) *largest_group = grp_rows_ >= 0 ? grp_largest_ : 0;
+  if (last_engines) *last_engines = grp_last_engines_;
+  if (last_scan_queries) *last_scan_queries = grp_last_scan_queries_;
+  return EPS_OK;
+}
+
+// The k closest groups per query (groups.hip).  Pages: a round is a page of keys per unfinished query, groups_first_kernel over it, and one host
+// sync that reads how many queries are left.  Scan: the table once per 4 queries into the (query, label) slots, c queries at a time.  AUTO:
+// GROUPS_AUTO_ROUNDS rounds of pages, then the scan for the queries still unfinished, named by number as search_range's fall-backs are.
+// Reports like a search (statistics, kernel ring); changes nothing a later search can observe.
+int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* pp, int32_t engine, int32_t page_rows, int64_t scratch_bytes,
+                             int64_t* ids, float* dist, int64_t* group_keys, int32_t* counts) {
+  eps_search_params p;
+  if (pp) p = *pp; else eps_default_search_params(&p);
+  const char* why;
+  if (groups_args_check(nq, k, engine, page_rows, scratch_bytes, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_groups: ") + why);
+  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_groups: unknown flat engine");
+  if (nq == 0) return EPS_OK;
+  HIP_TRY(hipSetDevice(device_));
+  if (grp_rows_ < 0) return fail(EPS_USER_ERROR, "search_groups: no groups are set: call set_groups first");
+  if (grp_version_ != rows_version_ || grp_rows_ != n_rows_)
+    return fail(EPS_USER_ERROR, "search_groups: the group labels are stale (rows were attached or appended): call set_groups again");
+  if (!queries || !ids || !dist || !group_keys) return fail(EPS_USER_ERROR, "search_groups: null buffer");
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || out_dev != is_device_ptr(group_keys) || (counts && out_dev != is_device_ptr(counts)))
+    return fail(EPS_USER_ERROR, "search_groups: ids_out, dist_out, group_keys_out and counts_out must all be host or all be device pointers");
+  int32_t rc = check_filters_cover_table("search_groups");
+  if (rc != EPS_OK) return rc;
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the row's exact distance)
+  grp_last_engines_ = 0;
+  grp_last_scan_queries_ = 0;
+
+  const float* dq;
+  rc = stage_queries("search_groups", queries, nq, &dq, !out_dev);
+  if (rc != EPS_OK) return rc;
+
+  // ---- scratch: result keys; [lo | compacted lo | counts | status | query numbers]; a page; the compacted queries; host results' device block
+  const int64_t n = n_rows_, G = grp_n_groups_;
+  const int P = groups_page_rows(k, page_rows);
+  const bool pages = engine != EPS_GROUPS_SCAN && n > 0;
+  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float);
+  const size_t out_bytes = 2 * ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
+  if (!grp_res_.reserve((size_t)nq * k * sizeof(u64)) || !grp_state_.reserve((size_t)nq * 28) ||
+      (pages && (!grp_page_.reserve((size_t)nq * P * sizeof(u64)) || !grp_q_.reserve((size_t)nq * dim_ * sizeof(float)))) ||
+      (!out_dev && !grp_out_.reserve(out_bytes)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (scratch)");
+  if (!h_grp_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of page-locked host memory");
+  u64* res = grp_res_.as<u64>();
+  u64* d_lo = grp_state_.as<u64>();
+  u64* d_clo = d_lo + nq;
+  u32* d_rescnt = reinterpret_cast<u32*>(d_clo + nq);
+  u32* d_status = d_rescnt + nq;
+  int32_t* d_qsel = reinterpret_cast<int32_t*>(d_status + nq);
+  u32* h_left = static_cast<u32*>(h_grp_.p);
+  const int32_t* label = grp_label_.as<int32_t>();
+  int64_t* d_ids = ids;
+  int64_t* d_gk = group_keys;
+  float* d_dist = dist;
+  int32_t* d_cnt = counts;
+  if (!out_dev) {
+    d_ids = grp_out_.as<int64_t>();
+    d_gk = reinterpret_cast<int64_t*>(grp_out_.as<char>() + ids_bytes);
+    d_dist = reinterpret_cast<float*>(grp_out_.as<char>() + 2 * ids_bytes);
+    d_cnt = reinterpret_cast<int32_t*>(grp_out_.as<char>() + 2 * ids_bytes + dist_bytes);
+  }
+  launch_fill_u64(res, nq * k, KEY_EMPTY, stream_);
+  HIP_TRY(hipMemsetAsync(d_rescnt, 0, (size_t)nq * 8, stream_));   // (counts and status)
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  int64_t left = n > 0 ? nq : 0;   // queries without their answer yet; after a round of pages d_qsel names them
+  bool named = false;
+  if (pages) {
+    u64* page = grp_page_.as<u64>();
+    for (int round = 0; left > 0 && (engine == EPS_GROUPS_PAGES || round < GROUPS_AUTO_ROUNDS); ++round) {
+      if (round == 0) {   // the flat engine a search of (nq, P) would take; all of them carry the stream scan's bits
+        int fe = p.flat_engine;
+        const int bits = fe == EPS_FLAT_MFMA ? 16 : (fe == EPS_FLAT_MFMA_I8 ? 8 : 0);
+        if (fe == EPS_FLAT_MFMA_I8) fe = EPS_FLAT_MFMA;
+        if (fe == EPS_FLAT_AUTO) {   // (the rule counts single-query calls towards building a mirror: that is a search's business)
+          const int64_t keep_version = small_calls_version_;
+          const int keep_calls = small_calls_;
+          fe = flat_mfma_profitable(*this, nq, P) ? EPS_FLAT_MFMA : EPS_FLAT_STREAM;
+          small_calls_version_ = keep_version;
+          small_calls_ = keep_calls;
+        }
+        if (prog_len_ > 0 && prog_uses_dist_) fe = EPS_FLAT_STREAM;   // (a filter on @distance needs exact distances where it is evaluated)
+        rc = fe == EPS_FLAT_MFMA ? flat_mfma_search(*this, dq, nq, P, page, false, bits) : flat_stream_page(dq, nq, P, 0, n, page, -1, true, nullptr, 0);
+      } else {
+        launch_groups_gather(dq, (int)dim_, d_lo, d_qsel, left, grp_q_.as<float>(), d_clo, stream_);
+        rc = flat_stream_page(grp_q_.as<float>(), left, P, 0, n, page, -1, true, d_clo, 1);
+      }
+      if (rc != EPS_OK) return rc;
+      launch_groups_first(GroupsFirstArgs{page, P, left, named ? d_qsel : nullptr, label, k, res, d_rescnt, d_status, d_lo}, stream_);
+      launch_groups_compact(d_status, nq, d_qsel, h_left, stream_);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(stream_));   // the round's one sync
+      left = (int64_t)*h_left;
+      named = true;
+    }
+    grp_last_engines_ |= 1 << EPS_GROUPS_PAGES;
+  }
+  if (left > 0 && engine != EPS_GROUPS_PAGES) {
+    const GroupsScanPlan plan = groups_scan_plan(left, G, k, scratch_bytes);
+    if (!grp_table_.reserve((size_t)groups_table_bytes(plan, G)) || !partial_buf_.reserve((size_t)plan.c * plan.W * k * sizeof(u64)) ||
+        !grp_run_.reserve((size_t)plan.c * k * sizeof(u64)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (the scan's table)");
+    u64* best = grp_table_.as<u64>();
+    const FilterSpec fs = filter_spec();
+    for (int64_t i0 = 0; i0 < left; i0 += plan.c) {
+      const int64_t mc = std::min(plan.c, left - i0);
+      launch_fill_u64(best, mc * G, KEY_EMPTY, stream_);
+      GroupsScanArgs a;
+      a.rows = d_rows_;
+      a.n = n;
+      a.dim = (int)dim_;
+      a.metric = metric_;
+      a.queries = named ? dq : dq + i0 * dim_;   // (unnamed: query numbers count from the chunk's first)
+      a.m = mc;
+      a.qsel = named ? d_qsel + i0 : nullptr;
+      a.f = fs;
+      a.label = label;
+      a.best = best;
+      a.G = G;
+      a.W = flat_scan_waves(n, mc, (int)dim_);
+      HIP_TRY(hipEventRecord(evk0_, stream_));
+      launch_groups_min_scan(a, stream_);
+      HIP_TRY(hipEventRecord(evk1_, stream_));
+      launch_groups_table_topk(best, G, mc, k, plan, partial_buf_.as<u64>(), stream_);
+      launch_among_merge(partial_buf_.as<u64>(), plan.W, k, mc, grp_run_.as<u64>(), stream_);
+      launch_groups_scatter(grp_run_.as<u64>(), k, a.qsel, mc, named ? res : res + i0 * k, stream_);
+      stats_.main_kernel_queries = mc;
+    }
+    stats_.main_kernel_launches = 1;
+    stats_.main_kernel_rows = n;
+    stats_.main_kernel_bits = 32;
+    stats_.dist_evals += left * n;
+    grp_last_engines_ |= 1 << EPS_GROUPS_SCAN;
+    grp_last_scan_queries_ = left;
+  }
+  launch_finalize(res, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
+  launch_groups_keys(res, nq, k, label, grp_keys_.as<int64_t>(), d_gk, stream_);
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, ids_bytes, ids_bytes}, {dist, 2 * ids_bytes, dist_bytes},
+                                               {counts, 2 * ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());

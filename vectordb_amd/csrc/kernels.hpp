@@ -6,6 +6,7 @@
 
 #include "among_host.hpp"
 #include "device_common.hpp"
+#include "groups_host.hpp"
 #include "merge_host.hpp"
 #include "sparse_host.hpp"
 #include "sparse_inv_host.hpp"
@@ -203,6 +204,46 @@ struct AmongArgs {
 // the gather (in slices of AMONG_GRID_Y query tiles), then the merge of every query's partial lists into run_keys[nq][k]: sorted, unique
 void launch_among_gather(const AmongArgs& a, hipStream_t s);
 void launch_among_merge(const u64* partial, int W, int k, int64_t nq, u64* run_keys, hipStream_t s);
+
+// ---------------------------------------------------------------- grouped search (eps_index_search_groups; groups.hip, plan: groups_host.hpp)
+constexpr u32 GROUPS_UNFINISHED = 1;   // a query's status while it holds fewer than k representatives and its last page was full
+struct GroupsFirstArgs {     // one round of the page engine: the first occurrences of a page's labels, appended to the queries' results
+  const u64* page;           // [m][P] launch-local query i's page: ascending keys, KEY_EMPTY behind the last
+  int P;
+  int64_t m;                 // queries of this launch
+  const int32_t* qsel;       // [m] their query numbers, or null: 0 .. m - 1
+  const int32_t* label;      // [n_rows]
+  int k;
+  u64* res_keys;             // [..][k] by query number: the representatives so far, ascending, KEY_EMPTY behind them
+  u32* res_cnt;              // [..]
+  u32* status;               // [..] GROUPS_UNFINISHED or 0
+  u64* lo;                   // [..] the page's last key: the next page continues after it
+};
+void launch_groups_first(const GroupsFirstArgs& a, hipStream_t s);
+// the queries whose status is GROUPS_UNFINISHED, in ascending order: qsel[0 .. *m_out), *m_out (a host-mapped word) their number.  One workgroup
+void launch_groups_compact(const u32* status, int64_t nq, int32_t* qsel, u32* m_out, hipStream_t s);
+// the queries named by qsel and their continuation keys, copied next to each other
+void launch_groups_gather(const float* queries, int dim, const u64* lo, const int32_t* qsel, int64_t m, float* q_out, u64* lo_out, hipStream_t s);
+struct GroupsScanArgs {      // the scan engine: every visible row offers its key to its group's slot
+  const float* rows;
+  int64_t n;
+  int dim, metric;
+  const float* queries;      // [..][dim], indexed by query number
+  int64_t m;                 // queries of this launch (one chunk of the plan)
+  const int32_t* qsel;       // [m] their query numbers, or null: 0 .. m - 1
+  FilterSpec f;
+  const int32_t* label;      // [n]
+  u64* best;                 // [m][G] launch-local query i's slots, KEY_EMPTY before the launch
+  int64_t G;
+  int W;                     // wavefronts over the rows = gridDim.x * 4
+};
+void launch_groups_min_scan(const GroupsScanArgs& a, hipStream_t s);
+// partial[i][w][k] = the k smallest keys of slice w of query i's slots (sorted, KEY_EMPTY behind them)
+void launch_groups_table_topk(const u64* best, int64_t G, int64_t m, int k, const GroupsScanPlan& plan, u64* partial, hipStream_t s);
+// res_keys[qsel[i]][..] = run_keys[i][..] (qsel null: i)
+void launch_groups_scatter(const u64* run_keys, int k, const int32_t* qsel, int64_t m, u64* res_keys, hipStream_t s);
+// group_keys[q][e] = key_of_label[label[row of res_keys[q][e]]], 0 where the slot is unused
+void launch_groups_keys(const u64* res_keys, int64_t nq, int k, const int32_t* label, const int64_t* key_of_label, int64_t* group_keys, hipStream_t s);
 
 // ---------------------------------------------------------------- sparse-vector scan (eps_sparse_index_*; sparse.hip, plan: sparse_host.hpp)
 struct SparseVerdict {          // what sparse_validate_kernel leaves: ~0 / 0 before the launch

@@ -370,6 +370,16 @@ class ShardGroup : public IndexBase {
     return EPS_OK;
   }
 
+  // (a group's rows may lie on several shards: its representative would need a merge by group, which the exchange does not have)
+  int32_t set_groups(const int64_t*, int64_t) override {
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
+  }
+  int32_t search_groups(const float*, int64_t, int32_t, const eps_search_params*, int32_t, int32_t, int64_t, int64_t*, float*, int64_t*, int32_t*) override {
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
+  }
+  int32_t groups_info(int64_t*, int64_t*, int32_t*, int64_t*) override {
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
+  }
   int64_t row_count() const override { return n_rows_; }
   int32_t last_stats(eps_search_stats* out) override {   // counters summed over the shards, times = the slowest shard
     eps_search_stats t;

@@ -501,6 +501,70 @@ class GpuIndex:
                                                   _ptr(dist), _ptr(counts)))
         return out_ids, dist, counts
 
+    def set_groups(self, keys):
+        """eps_index_set_groups: one int64 key per row (NumPy, or a contiguous 1-D int64 device tensor); rows with equal keys form a group.  None
+        forgets the groups.  After attach_rows / append_rows the keys must be set again."""
+        if keys is None:
+            self._check(self.L.eps_index_set_groups(self.h, None, 0))
+            return
+        if _is_dev(keys):
+            if str(keys.dtype) != "torch.int64" or keys.dim() != 1 or not keys.is_contiguous():
+                raise ValueError("set_groups: device keys must be a contiguous 1-D int64 tensor, got %s %s" % (keys.dtype, tuple(keys.shape)))
+            n = keys.numel()
+        else:
+            keys = np.ascontiguousarray(keys, np.int64).reshape(-1)
+            n = keys.size
+        self._check(self.L.eps_index_set_groups(self.h, _ptr(keys), n))   # (the library copies the keys before it returns)
+
+    def search_groups(self, queries, k, engine="auto", page_rows=0, scratch_bytes=0, flat_engine="auto", out=None):
+        """eps_index_search_groups: per query the k closest GROUPS (set_groups), each represented by its closest visible row.  Returns
+        (ids int64[nq, k], dist float32[nq, k], group_keys int64[nq, k], counts int32[nq]) in ascending (distance, id) order of the
+        representatives; counts = min(k, groups with a visible row), the rest -1 / +inf / key 0.  The distances are a flat search's, bit for bit.
+        engine: "auto" | "pages" | "scan" (or a GROUPS_* value), flat_engine as for search_range: the same bits from all of them.  page_rows: keys per
+        page (0: the library's rule of k); scratch_bytes: a cap on the scan engine's table (0: the default).  NumPy queries give NumPy results; device
+        queries give device tensors and the call is asynchronous on the index's stream.  out=(ids, dist, group_keys, counts): caller-provided
+        buffers, all NumPy or all device."""
+        k = int(k)
+        engine, flat_engine = GROUPS_ENGINES[engine], RANGE_ENGINES[flat_engine]
+        dev = _is_dev(queries)
+        if not dev:
+            queries = np.ascontiguousarray(queries, np.float32)
+            if queries.ndim == 1:
+                queries = queries[None, :]
+        nq = queries.shape[0]
+        assert queries.shape[1] == self.dim
+        if out is not None:
+            ids, dist, gkeys, counts = out
+            if len({_is_dev(a) for a in out}) != 1:
+                raise ValueError("search_groups: out[ids], out[dist], out[group_keys] and out[counts] must all be NumPy arrays or all be device tensors")
+            _check_out(ids, "ids", (nq, k), "int64")
+            _check_out(dist, "dist", (nq, k), "float32")
+            _check_out(gkeys, "group_keys", (nq, k), "int64")
+            _check_out(counts, "counts", (nq,), "int32")
+        elif dev:
+            import torch
+            ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
+            dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=queries.device)
+            gkeys = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+        else:
+            ids = np.empty((nq, max(k, 0)), np.int64)
+            dist = np.empty((nq, max(k, 0)), np.float32)
+            gkeys = np.empty((nq, max(k, 0)), np.int64)
+            counts = np.empty(nq, np.int32)
+        p = self.params(flat_engine=flat_engine)
+        self._keep["groups"] = (queries,)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_groups(self.h, _ptr(queries), nq, k, C.byref(p), engine, int(page_rows), int(scratch_bytes),
+                                                   _ptr(ids), _ptr(dist), _ptr(gkeys), _ptr(counts)))
+        return ids, dist, gkeys, counts
+
+    def groups_info(self):
+        """eps_index_groups_info: {"n_groups", "largest_group", "last_engines": the engines the last search_groups ran, as names, "last_scan_queries"}"""
+        g, big, scanned, engines = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._check(self.L.eps_index_groups_info(self.h, C.byref(g), C.byref(big), C.byref(engines), C.byref(scanned)))
+        return {"n_groups": g.value, "largest_group": big.value, "last_scan_queries": scanned.value,
+                "last_engines": tuple(name for name, bit in (("pages", GROUPS_PAGES), ("scan", GROUPS_SCAN)) if engines.value >> bit & 1)}
+
     def kernel_times(self, cap=64):
         """main-kernel ms of the most recent search calls (oldest first); synchronises the index's stream"""
         buf = (C.c_double * cap)()
@@ -524,6 +588,10 @@ def _check_out(a, name, shape, dtype):
 
 RANGE_ENGINES = {"auto": FLAT_AUTO, "stream": FLAT_STREAM, "mfma": FLAT_MFMA, "mfma_i8": FLAT_MFMA_I8,
                  FLAT_AUTO: FLAT_AUTO, FLAT_STREAM: FLAT_STREAM, FLAT_MFMA: FLAT_MFMA, FLAT_MFMA_I8: FLAT_MFMA_I8}
+
+
+GROUPS_AUTO, GROUPS_PAGES, GROUPS_SCAN = 0, 1, 2
+GROUPS_ENGINES = {"auto": GROUPS_AUTO, "pages": GROUPS_PAGES, "scan": GROUPS_SCAN, GROUPS_AUTO: GROUPS_AUTO, GROUPS_PAGES: GROUPS_PAGES, GROUPS_SCAN: GROUPS_SCAN}
 
 
 def _check_range_out(ids, dist, counts, totals, nq, cap):
