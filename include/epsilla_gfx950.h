@@ -30,6 +30,8 @@
  *                                   of the rows the CALLER names - the allow-list search, the second stage of a hybrid search
  *   eps_index_search_groups         (new) the k closest groups of rows, each by its closest row; the reference's relative is the host-side
  *                                   grouping of a finished answer (FacetExecutor, db/execution/aggregation.hpp) - it has no grouped search
+ *   eps_index_search_group_rows     (new) ... and of each of those groups its m closest rows and the number of its visible rows: the
+ *                                   `group_size` of a grouped search; the reference has no relative
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
  *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
@@ -507,6 +509,33 @@ int32_t eps_index_set_groups(eps_index* h, const int64_t* keys, int64_t n);
 int32_t eps_index_search_groups(eps_index* h, const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
                                 int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out);
 int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries);
+/* Grouped search, m rows per group: the k closest groups of eps_index_search_groups and of each its m closest rows - "the m best chunks of each of
+ * the k best documents", and how many chunks of each document matched at all.  Before, a caller ran eps_index_search_groups, copied the keys to
+ * the host, built a candidate list per (query, group) pair from its own copy of the keys and called eps_index_search_among with nq x k
+ * pseudo-queries.
+ * The rule, for query j, with V_j, the distance bits and the (distance, row) key order - NaN after +inf, ties to the smaller row - exactly as
+ * eps_index_search_groups defines them.  The groups, their order, group_keys_out [nq][k] and counts_out [nq] (may be NULL) are those of
+ * eps_index_search_groups with the same k, p, engine, page_rows and scratch_bytes.  For the s-th group g of query j, ids_out[j][s][0 .. c) (through
+ * eps_index_set_id_map) and dist_out[j][s][0 .. c) are the c = min(m, |V_j n g|) smallest keys of V_j n g in ascending order, so slot 0 is the
+ * representative eps_index_search_groups returns; row_counts_out[j][s] = c; group_sizes_out[j][s] (may be NULL) = |V_j n g|, the visible rows of
+ * the group for this query (under a program on `@distance` it depends on the query).  Unused row slots: -1 / +inf; unused group slots: key 0, row
+ * count 0, size 0.  Equivalently: walk V_j in ascending key order, admit a group on its first row until k groups are admitted, keep a row iff
+ * its group is admitted and holds fewer than m rows; every visible row of an admitted group counts towards its size.
+ * ids_out, dist_out [nq][k][m]; group_keys_out, row_counts_out, group_sizes_out [nq][k].  1 <= k <= 1024, 1 <= m <= 1024, k * m <= 65536, else
+ * EPS_USER_ERROR; nq = 0: EPS_OK.  queries and the outputs: host or device, the outputs all of one kind - device: on the index's stream, the
+ * caller synchronises (with EPS_GROUPS_SCAN the call has no host sync at all); host: the call synchronises.  No groups set, stale labels, stale
+ * filters, a null required buffer, an unknown engine, outputs of mixed kinds: the errors of eps_index_search_groups.
+ * The first call after eps_index_set_groups builds the rows by group on the device (csrc/group_rows.hip: a histogram of the labels, a scan, a
+ * scatter: a set-up step with one stream sync, 4 n + 8 (G + 1) bytes kept until the labels go - eps_index_set_groups, or the refusal of stale
+ * labels; a failed allocation: EPS_INFRA_UNEXPECTED_ERROR).  After the first phase a kernel lists, per (query, group) pair, the chunks of 256 rows
+ * of its group (more where a group is huge: csrc/group_rows_host.hpp); a fixed grid of wavefronts strides over that list, each chunk into a
+ * sorted list of m keys and a count of its visible rows, and a merge per pair follows: a group of any size is spread over the chip.
+ * eps_index_groups_info reports what the equivalent eps_index_search_groups call would have left; eps_index_last_stats reports the call like a
+ * search: dist_evals includes the (row, query) pairs of the second phase, main_kernel_ms is its gather.  A sharded handle:
+ * EPS_DB_UNSUPPORTED_ERROR.  Nothing a later call can observe changes. */
+int32_t eps_index_search_group_rows(eps_index* h, const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine,
+                                    int32_t page_rows, int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out,
+                                    int32_t* row_counts_out, int64_t* group_sizes_out, int32_t* counts_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

@@ -272,6 +272,11 @@ int32_t eps_index_search_groups(eps_index* h, const float* q, int64_t nq, int32_
                                 int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* counts) {
   GUARD(h, IX(h)->search_groups(q, nq, k, p, engine, page_rows, scratch_bytes, ids, dist, group_keys, counts));
 }
+int32_t eps_index_search_group_rows(eps_index* h, const float* q, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                                    int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* row_counts, int64_t* group_sizes,
+                                    int32_t* counts) {
+  GUARD(h, IX(h)->search_group_rows(q, nq, k, m, p, engine, page_rows, scratch_bytes, ids, dist, group_keys, row_counts, group_sizes, counts));
+}
 int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) {
   GUARD(h, IX(h)->groups_info(n_groups, largest_group, last_engines, last_scan_queries));
 }

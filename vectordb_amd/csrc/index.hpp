@@ -121,6 +121,9 @@ class IndexBase {
   virtual int32_t search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
                                 int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out) = 0;
   virtual int32_t groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) = 0;
+  virtual int32_t search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                                    int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* row_counts_out,
+                                    int64_t* group_sizes_out, int32_t* counts_out) = 0;
   virtual int64_t row_count() const = 0;
   virtual int32_t last_stats(eps_search_stats* out) = 0;
   virtual int kernel_times(double* ms_out, int cap) = 0;
@@ -186,6 +189,11 @@ class Index : public IndexBase {
   int32_t search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows, int64_t scratch_bytes,
                         int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* counts_out) override;
   int32_t groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) override;
+  // ... and of each of them its m closest visible rows and the number of its visible rows (eps_index_search_group_rows; group_rows.hip, plan:
+  // group_rows_host.hpp)
+  int32_t search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine, int32_t page_rows,
+                            int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* row_counts_out, int64_t* group_sizes_out,
+                            int32_t* counts_out) override;
 
   int64_t row_count() const override { return n_rows_; }
 
@@ -263,6 +271,14 @@ class Index : public IndexBase {
   HostBuf h_grp_;
   int64_t grp_n_groups_ = 0, grp_largest_ = 0, grp_rows_ = -1, grp_version_ = -1, grp_last_scan_queries_ = 0;
   int32_t grp_last_engines_ = 0;
+  // search_group_rows(): the rows by group - offsets[G + 1], rows[n] - built at the first call after a set_groups (grp_by_group_) and released with
+  // the labels; [pair counter | sizes | work-item prefix] of a pass; the pairs' merged lists
+  DevBuf grp_offsets_, grp_rowlist_, grp_work_, grp_rows_run_;
+  bool grp_by_group_ = false;
+  int32_t groups_ready(const char* who);
+  void forget_rows_by_group();
+  int32_t groups_representatives(const char* who, const float* dq, int64_t nq, int32_t k, const eps_search_params& p, int32_t engine, int32_t page_rows,
+                                 int64_t scratch_bytes);
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   // main-kernel event pairs of the last KRING search calls (read back after a run without a sync inside it);
   // evk0_/evk1_ alias the pair of the call in progress

@@ -1,4 +1,4 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, the steps they share, and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, the steps they share, and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
@@ -582,6 +582,7 @@ int32_t Index::set_groups(const int64_t* keys, int64_t n) {
   HIP_TRY(hipSetDevice(device_));
   HIP_TRY(hipStreamSynchronize(stream_));   // (a call in flight may read the labels this one replaces)
   grp_rows_ = -1;   // forgotten, also where the call fails below
+  forget_rows_by_group();
   grp_n_groups_ = grp_largest_ = 0;
   if (!keys) return EPS_OK;
   if (n != n_rows_) return fail(EPS_USER_ERROR, "set_groups: n must equal the table's row count");
@@ -630,43 +631,23 @@ int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const 
   if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_groups: unknown flat engine");
   if (nq == 0) return EPS_OK;
   HIP_TRY(hipSetDevice(device_));
-  if (grp_rows_ < 0) return fail(EPS_USER_ERROR, "search_groups: no groups are set: call set_groups first");
-  if (grp_version_ != rows_version_ || grp_rows_ != n_rows_)
-    return fail(EPS_USER_ERROR, "search_groups: the group labels are stale (rows were attached or appended): call set_groups again");
+  int32_t rc = groups_ready("search_groups");
+  if (rc != EPS_OK) return rc;
   if (!queries || !ids || !dist || !group_keys) return fail(EPS_USER_ERROR, "search_groups: null buffer");
   const bool out_dev = is_device_ptr(ids);
   if (out_dev != is_device_ptr(dist) || out_dev != is_device_ptr(group_keys) || (counts && out_dev != is_device_ptr(counts)))
     return fail(EPS_USER_ERROR, "search_groups: ids_out, dist_out, group_keys_out and counts_out must all be host or all be device pointers");
-  int32_t rc = check_filters_cover_table("search_groups");
+  rc = check_filters_cover_table("search_groups");
   if (rc != EPS_OK) return rc;
   begin_timed_call();
   prefilter_call_ = false;   // (@distance reads the row's exact distance)
-  grp_last_engines_ = 0;
-  grp_last_scan_queries_ = 0;
 
   const float* dq;
   rc = stage_queries("search_groups", queries, nq, &dq, !out_dev);
   if (rc != EPS_OK) return rc;
-
-  // ---- scratch: result keys; [lo | compacted lo | counts | status | query numbers]; a page; the compacted queries; host results' device block
-  const int64_t n = n_rows_, G = grp_n_groups_;
-  const int P = groups_page_rows(k, page_rows);
-  const bool pages = engine != EPS_GROUPS_SCAN && n > 0;
   const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float);
   const size_t out_bytes = 2 * ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
-  if (!grp_res_.reserve((size_t)nq * k * sizeof(u64)) || !grp_state_.reserve((size_t)nq * 28) ||
-      (pages && (!grp_page_.reserve((size_t)nq * P * sizeof(u64)) || !grp_q_.reserve((size_t)nq * dim_ * sizeof(float)))) ||
-      (!out_dev && !grp_out_.reserve(out_bytes)))
-    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (scratch)");
-  if (!h_grp_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of page-locked host memory");
-  u64* res = grp_res_.as<u64>();
-  u64* d_lo = grp_state_.as<u64>();
-  u64* d_clo = d_lo + nq;
-  u32* d_rescnt = reinterpret_cast<u32*>(d_clo + nq);
-  u32* d_status = d_rescnt + nq;
-  int32_t* d_qsel = reinterpret_cast<int32_t*>(d_status + nq);
-  u32* h_left = static_cast<u32*>(h_grp_.p);
-  const int32_t* label = grp_label_.as<int32_t>();
+  if (!out_dev && !grp_out_.reserve(out_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (scratch)");
   int64_t* d_ids = ids;
   int64_t* d_gk = group_keys;
   float* d_dist = dist;
@@ -677,6 +658,45 @@ int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const 
     d_dist = reinterpret_cast<float*>(grp_out_.as<char>() + 2 * ids_bytes);
     d_cnt = reinterpret_cast<int32_t*>(grp_out_.as<char>() + 2 * ids_bytes + dist_bytes);
   }
+  rc = groups_representatives("search_groups", dq, nq, k, p, engine, page_rows, scratch_bytes);
+  if (rc != EPS_OK) return rc;
+  const u64* res = grp_res_.as<u64>();
+  launch_finalize(res, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
+  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), d_gk, stream_);
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, ids_bytes, ids_bytes}, {dist, 2 * ids_bytes, dist_bytes},
+                                               {counts, 2 * ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
+// The first phase of search_groups and search_group_rows, after their checks and begin_timed_call: the engines, which leave query j's
+// representatives in grp_res_[j][k] - ascending keys, KEY_EMPTY behind them - and the call's first event (ev0_) on the stream.
+int32_t Index::groups_representatives(const char* who, const float* dq, int64_t nq, int32_t k, const eps_search_params& p, int32_t engine, int32_t page_rows,
+                                      int64_t scratch_bytes) {
+  int32_t rc;
+  grp_last_engines_ = 0;
+  grp_last_scan_queries_ = 0;
+  // ---- scratch: result keys; [lo | compacted lo | counts | status | query numbers]; a page; the compacted queries
+  const int64_t n = n_rows_, G = grp_n_groups_;
+  const int P = groups_page_rows(k, page_rows);
+  const bool pages = engine != EPS_GROUPS_SCAN && n > 0;
+  if (!grp_res_.reserve((size_t)nq * k * sizeof(u64)) || !grp_state_.reserve((size_t)nq * 28) ||
+      (pages && (!grp_page_.reserve((size_t)nq * P * sizeof(u64)) || !grp_q_.reserve((size_t)nq * dim_ * sizeof(float)))))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of device memory (scratch)");
+  if (!h_grp_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of page-locked host memory");
+  u64* res = grp_res_.as<u64>();
+  u64* d_lo = grp_state_.as<u64>();
+  u64* d_clo = d_lo + nq;
+  u32* d_rescnt = reinterpret_cast<u32*>(d_clo + nq);
+  u32* d_status = d_rescnt + nq;
+  int32_t* d_qsel = reinterpret_cast<int32_t*>(d_status + nq);
+  u32* h_left = static_cast<u32*>(h_grp_.p);
+  const int32_t* label = grp_label_.as<int32_t>();
   launch_fill_u64(res, nq * k, KEY_EMPTY, stream_);
   HIP_TRY(hipMemsetAsync(d_rescnt, 0, (size_t)nq * 8, stream_));   // (counts and status)
   HIP_TRY(hipEventRecord(ev0_, stream_));
@@ -717,7 +737,7 @@ int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const 
     const GroupsScanPlan plan = groups_scan_plan(left, G, k, scratch_bytes);
     if (!grp_table_.reserve((size_t)groups_table_bytes(plan, G)) || !partial_buf_.reserve((size_t)plan.c * plan.W * k * sizeof(u64)) ||
         !grp_run_.reserve((size_t)plan.c * k * sizeof(u64)))
-      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (the scan's table)");
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of device memory (the scan's table)");
     u64* best = grp_table_.as<u64>();
     const FilterSpec fs = filter_spec();
     for (int64_t i0 = 0; i0 < left; i0 += plan.c) {
@@ -751,12 +771,151 @@ int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const 
     grp_last_engines_ |= 1 << EPS_GROUPS_SCAN;
     grp_last_scan_queries_ = left;
   }
-  launch_finalize(res, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
-  launch_groups_keys(res, nq, k, label, grp_keys_.as<int64_t>(), d_gk, stream_);
+  return EPS_OK;
+}
+
+// no groups set / labels of another table: the refusals search_groups and search_group_rows share.  Stale labels take the rows by group with them
+int32_t Index::groups_ready(const char* who) {
+  if (grp_rows_ < 0) return fail(EPS_USER_ERROR, std::string(who) + ": no groups are set: call set_groups first");
+  if (grp_version_ != rows_version_ || grp_rows_ != n_rows_) {
+    forget_rows_by_group();
+    return fail(EPS_USER_ERROR, std::string(who) + ": the group labels are stale (rows were attached or appended): call set_groups again");
+  }
+  return EPS_OK;
+}
+
+void Index::forget_rows_by_group() {
+  if (!grp_by_group_ && !grp_offsets_.p && !grp_rowlist_.p) return;
+  (void)hipStreamSynchronize(stream_);   // (a call in flight may read them)
+  grp_offsets_.release();
+  grp_rowlist_.release();
+  grp_by_group_ = false;
+}
+
+// The k closest groups per query and the m closest visible rows of each (group_rows.hip, plan: group_rows_host.hpp).  Phase 1 is search_groups'
+// (groups_representatives); phase 2 - work list, gather, merge, result conversion - reads what phase 1 left on the device and has no host sync of
+// its own, so with EPS_GROUPS_SCAN and device results the call stays asynchronous.  The rows by group (offsets[G + 1], rows[n]) are built on the
+// device at the first call after a set_groups.  Reports like a search; changes nothing a later call can observe.
+int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* pp, int32_t engine, int32_t page_rows,
+                                 int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* row_counts, int64_t* group_sizes,
+                                 int32_t* counts) {
+  eps_search_params p;
+  if (pp) p = *pp; else eps_default_search_params(&p);
+  const char* why;
+  if (group_rows_args_check(nq, k, m, engine, page_rows, scratch_bytes, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_group_rows: ") + why);
+  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_group_rows: unknown flat engine");
+  if (nq == 0) return EPS_OK;
+  HIP_TRY(hipSetDevice(device_));
+  int32_t rc = groups_ready("search_group_rows");
+  if (rc != EPS_OK) return rc;
+  if (!queries || !ids || !dist || !group_keys || !row_counts) return fail(EPS_USER_ERROR, "search_group_rows: null buffer");
+  const bool out_dev = is_device_ptr(ids);
+  if (out_dev != is_device_ptr(dist) || out_dev != is_device_ptr(group_keys) || out_dev != is_device_ptr(row_counts) ||
+      (group_sizes && out_dev != is_device_ptr(group_sizes)) || (counts && out_dev != is_device_ptr(counts)))
+    return fail(EPS_USER_ERROR, "search_group_rows: the output buffers must all be host or all be device pointers");
+  rc = check_filters_cover_table("search_group_rows");
+  if (rc != EPS_OK) return rc;
+
+  const int64_t n = n_rows_, G = grp_n_groups_;
+  if (!grp_by_group_ && n > 0) {   // the set-up step: histogram, scan, scatter
+    DevBuf cursor;
+    if (!grp_offsets_.reserve((size_t)(G + 1) * sizeof(int64_t)) || !grp_rowlist_.reserve((size_t)n * sizeof(int32_t)) || !cursor.reserve((size_t)G * sizeof(u32))) {
+      forget_rows_by_group();
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of device memory (the rows by group)");
+    }
+    HIP_TRY(hipMemsetAsync(cursor.p, 0, (size_t)G * sizeof(u32), stream_));
+    launch_group_rows_build(grp_label_.as<int32_t>(), n, G, cursor.as<u32>(), grp_offsets_.as<int64_t>(), grp_rowlist_.as<int32_t>(), stream_);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream_));   // (the cursors end here)
+    grp_by_group_ = true;
+  }
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the row's exact distance)
+
+  const float* dq;
+  rc = stage_queries("search_group_rows", queries, nq, &dq, !out_dev);
+  if (rc != EPS_OK) return rc;
+
+  // ---- scratch: [pair counter | sizes | prefix] of a pass, its partial lists and merged lists; host results' device block
+  const GroupRowsPlan plan = group_rows_plan(nq, k, m, n > 0 ? n : 1, grp_largest_ > 0 ? grp_largest_ : 1);
+  const int64_t km = (int64_t)k * m, pass_pairs = plan.slice * k;
+  const size_t ids_bytes = (size_t)nq * km * sizeof(int64_t), dist_bytes = (size_t)nq * km * sizeof(float), gk_bytes = (size_t)nq * k * sizeof(int64_t),
+               rc_bytes = (size_t)nq * k * sizeof(int32_t);
+  const size_t off_gk = ids_bytes, off_sizes = off_gk + gk_bytes, off_dist = off_sizes + gk_bytes, off_rc = off_dist + dist_bytes, off_cnt = off_rc + rc_bytes;
+  const size_t out_bytes = off_cnt + (size_t)nq * sizeof(int32_t);
+  if (!grp_work_.reserve(8 + (size_t)(2 * pass_pairs + 1) * sizeof(u32)) || !partial_buf_.reserve((size_t)plan.items * m * sizeof(u64)) ||
+      !grp_rows_run_.reserve((size_t)pass_pairs * m * sizeof(u64)) || (!out_dev && !grp_out_.reserve(out_bytes)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of device memory (scratch)");
+  if (!h_among_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of page-locked host memory");
+  unsigned long long* d_evals = grp_work_.as<unsigned long long>();
+  u32* d_sizes = reinterpret_cast<u32*>(d_evals + 1);
+  int64_t* d_ids = ids;
+  int64_t* d_gk = group_keys;
+  int64_t* d_gs = group_sizes;
+  float* d_dist = dist;
+  int32_t* d_rc = row_counts;
+  int32_t* d_cnt = counts;
+  if (!out_dev) {
+    char* o = grp_out_.as<char>();
+    d_ids = reinterpret_cast<int64_t*>(o);
+    d_gk = reinterpret_cast<int64_t*>(o + off_gk);
+    d_gs = reinterpret_cast<int64_t*>(o + off_sizes);
+    d_dist = reinterpret_cast<float*>(o + off_dist);
+    d_rc = reinterpret_cast<int32_t*>(o + off_rc);
+    d_cnt = reinterpret_cast<int32_t*>(o + off_cnt);
+  }
+
+  rc = groups_representatives("search_group_rows", dq, nq, k, p, engine, page_rows, scratch_bytes);
+  if (rc != EPS_OK) return rc;
+  const u64* res = grp_res_.as<u64>();
+  HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
+  for (int64_t q0 = 0; q0 < nq; q0 += plan.slice) {
+    GroupRowsArgs a;
+    a.rows = d_rows_;
+    a.dim = (int)dim_;
+    a.metric = metric_;
+    a.queries = dq + q0 * dim_;
+    a.pairs = std::min(plan.slice, nq - q0) * k;
+    a.k = k;
+    a.m = m;
+    a.f = filter_spec();
+    a.res_keys = res + q0 * k;
+    a.label = grp_label_.as<int32_t>();
+    a.offsets = grp_offsets_.as<int64_t>();
+    a.group_rows = grp_rowlist_.as<int32_t>();
+    a.chunk = plan.chunk;
+    a.sizes = d_sizes;
+    a.prefix = d_sizes + pass_pairs;
+    a.partial = partial_buf_.as<u64>();
+    a.items = plan.items;
+    a.waves = plan.waves;
+    a.run_keys = grp_rows_run_.as<u64>();
+    a.evals = d_evals;
+    HIP_TRY(hipMemsetAsync(d_sizes, 0, (size_t)a.pairs * sizeof(u32), stream_));
+    if (n > 0) {
+      HIP_TRY(hipEventRecord(evk0_, stream_));
+      launch_group_rows_gather(a, stream_);
+      HIP_TRY(hipEventRecord(evk1_, stream_));
+      launch_group_rows_merge(a, stream_);
+    } else {   // no row: no group
+      launch_fill_u64(a.run_keys, a.pairs * m, KEY_EMPTY, stream_);
+    }
+    launch_group_rows_finalize(a, id_base_, id_stride_, d_ids + q0 * km, d_dist + q0 * km, d_rc + q0 * k, d_gs ? d_gs + q0 * k : nullptr,
+                               d_cnt ? d_cnt + q0 : nullptr, stream_);
+  }
+  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), d_gk, stream_);
+  if (n > 0) {
+    stats_.main_kernel_launches = 1;
+    stats_.main_kernel_rows = n;
+    stats_.main_kernel_queries = nq;
+    stats_.main_kernel_bits = 32;
+  }
+  HIP_TRY(hipMemcpyAsync(h_among_.p, d_evals, 8, hipMemcpyDeviceToHost, stream_));   // (the second phase's pairs: last_stats adds them)
+  among_evals_pending_ = true;
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {
-    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, ids_bytes, ids_bytes}, {dist, 2 * ids_bytes, dist_bytes},
-                                               {counts, 2 * ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, off_gk, gk_bytes}, {group_sizes, off_sizes, gk_bytes}, {dist, off_dist, dist_bytes},
+                                               {row_counts, off_rc, rc_bytes}, {counts, off_cnt, (size_t)nq * sizeof(int32_t)}});
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
@@ -768,7 +927,7 @@ int32_t Index::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   // event timings are read lazily: the caller may have left the work in flight
   if (ev0_ && hipEventSynchronize(ev1_) == hipSuccess) {
-    if (among_evals_pending_) s.dist_evals = (int64_t)*static_cast<const unsigned long long*>(h_among_.p);   // (copied out in front of ev1_)
+    if (among_evals_pending_) s.dist_evals += (int64_t)*static_cast<const unsigned long long*>(h_among_.p);   // (counted on the device, copied out in front of ev1_)
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) s.kernel_ms = ms;
     if (s.main_kernel_launches > 0 && hipEventElapsedTime(&ms, evk0_, evk1_) == hipSuccess) s.main_kernel_ms = ms;

@@ -6,6 +6,7 @@
 
 #include "among_host.hpp"
 #include "device_common.hpp"
+#include "group_rows_host.hpp"
 #include "groups_host.hpp"
 #include "merge_host.hpp"
 #include "sparse_host.hpp"
@@ -244,6 +245,36 @@ void launch_groups_table_topk(const u64* best, int64_t G, int64_t m, int k, cons
 void launch_groups_scatter(const u64* run_keys, int k, const int32_t* qsel, int64_t m, u64* res_keys, hipStream_t s);
 // group_keys[q][e] = key_of_label[label[row of res_keys[q][e]]], 0 where the slot is unused
 void launch_groups_keys(const u64* res_keys, int64_t nq, int k, const int32_t* label, const int64_t* key_of_label, int64_t* group_keys, hipStream_t s);
+
+// ---------------------------------------------------------------- m rows per group (eps_index_search_group_rows; group_rows.hip, plan: group_rows_host.hpp)
+// the rows of every label next to each other: offsets[G + 1], group_rows[n] (any order inside a group); cursor: G words, zero before the launch
+void launch_group_rows_build(const int32_t* label, int64_t n, int64_t G, u32* cursor, int64_t* offsets, int32_t* group_rows, hipStream_t s);
+struct GroupRowsArgs {         // one pass of the second phase: the m closest visible rows of every (query, slot) pair's group
+  const float* rows;
+  int dim, metric;
+  const float* queries;        // [pairs / k][dim]: the pass's queries
+  int64_t pairs;               // queries of the pass * k
+  int k, m;
+  FilterSpec f;
+  const u64* res_keys;         // [pairs] the first phase's representatives, KEY_EMPTY where a query has fewer than k groups
+  const int32_t* label;        // [n]
+  const int64_t* offsets;      // [G + 1]
+  const int32_t* group_rows;   // [n]
+  int64_t chunk;               // rows of a group per work item
+  u32* prefix;                 // [pairs + 1] work items of the pairs in front; [pairs]: all of them (written by the launch, never read by the host)
+  u32* sizes;                  // [pairs] visible rows of the pair's group: zero before the launch
+  u64* partial;                // [items][m] a sorted list per work item
+  int64_t items;               // the plan's bound on the work items
+  int64_t waves;               // wavefronts of the gather's grid
+  u64* run_keys;               // [pairs][m] the merged lists
+  unsigned long long* evals;   // (row, query) pairs given a distance, added to
+};
+// the work list, then the gather over it
+void launch_group_rows_gather(const GroupRowsArgs& a, hipStream_t s);
+void launch_group_rows_merge(const GroupRowsArgs& a, hipStream_t s);
+// ids [pairs][m] through the id map, dist [pairs][m], row_counts [pairs], group_sizes [pairs] (may be null), counts [pairs / k] (may be null)
+void launch_group_rows_finalize(const GroupRowsArgs& a, int64_t id_base, int64_t id_stride, int64_t* ids, float* dist, int32_t* row_counts,
+                                int64_t* group_sizes, int32_t* counts, hipStream_t s);
 
 // ---------------------------------------------------------------- sparse-vector scan (eps_sparse_index_*; sparse.hip, plan: sparse_host.hpp)
 struct SparseVerdict {          // what sparse_validate_kernel leaves: ~0 / 0 before the launch

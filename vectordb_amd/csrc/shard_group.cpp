@@ -377,6 +377,10 @@ class ShardGroup : public IndexBase {
   int32_t search_groups(const float*, int64_t, int32_t, const eps_search_params*, int32_t, int32_t, int64_t, int64_t*, float*, int64_t*, int32_t*) override {
     return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
   }
+  int32_t search_group_rows(const float*, int64_t, int32_t, int32_t, const eps_search_params*, int32_t, int32_t, int64_t, int64_t*, float*, int64_t*, int32_t*,
+                            int64_t*, int32_t*) override {
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
+  }
   int32_t groups_info(int64_t*, int64_t*, int32_t*, int64_t*) override {
     return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
   }

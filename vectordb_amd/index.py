@@ -558,6 +558,55 @@ class GpuIndex:
                                                    _ptr(ids), _ptr(dist), _ptr(gkeys), _ptr(counts)))
         return ids, dist, gkeys, counts
 
+    def search_group_rows(self, queries, k, m, engine="auto", page_rows=0, scratch_bytes=0, flat_engine="auto", out=None):
+        """eps_index_search_group_rows: per query the k closest GROUPS as search_groups returns them, and of each its m closest visible rows.  Returns
+        (ids int64[nq, k, m], dist float32[nq, k, m], group_keys int64[nq, k], row_counts int32[nq, k], group_sizes int64[nq, k], counts int32[nq]):
+        the rows of a group in ascending (distance, id) order, slot 0 the representative of search_groups; row_counts = min(m, visible rows of the
+        group), group_sizes = its visible rows for this query, counts = min(k, groups with a visible row); unused row slots -1 / +inf, unused group
+        slots key 0, row count 0, size 0.  engine, page_rows, scratch_bytes, flat_engine: as for search_groups.  NumPy queries give NumPy results;
+        device queries give device tensors and the call is asynchronous on the index's stream.  out=(ids, dist, group_keys, row_counts, group_sizes,
+        counts): caller-provided buffers, all NumPy or all device."""
+        k, m = int(k), int(m)
+        engine, flat_engine = GROUPS_ENGINES[engine], RANGE_ENGINES[flat_engine]
+        dev = _is_dev(queries)
+        if not dev:
+            queries = np.ascontiguousarray(queries, np.float32)
+            if queries.ndim == 1:
+                queries = queries[None, :]
+        nq = queries.shape[0]
+        assert queries.shape[1] == self.dim
+        kk, mm = max(k, 0), max(m, 0)
+        if out is not None:
+            ids, dist, gkeys, rcounts, gsizes, counts = out
+            if len({_is_dev(a) for a in out}) != 1:
+                raise ValueError("search_group_rows: the out buffers must all be NumPy arrays or all be device tensors")
+            _check_out(ids, "ids", (nq, k, m), "int64")
+            _check_out(dist, "dist", (nq, k, m), "float32")
+            _check_out(gkeys, "group_keys", (nq, k), "int64")
+            _check_out(rcounts, "row_counts", (nq, k), "int32")
+            _check_out(gsizes, "group_sizes", (nq, k), "int64")
+            _check_out(counts, "counts", (nq,), "int32")
+        elif dev:
+            import torch
+            ids = torch.empty((nq, kk, mm), dtype=torch.int64, device=queries.device)
+            dist = torch.empty((nq, kk, mm), dtype=torch.float32, device=queries.device)
+            gkeys = torch.empty((nq, kk), dtype=torch.int64, device=queries.device)
+            rcounts = torch.empty((nq, kk), dtype=torch.int32, device=queries.device)
+            gsizes = torch.empty((nq, kk), dtype=torch.int64, device=queries.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+        else:
+            ids = np.empty((nq, kk, mm), np.int64)
+            dist = np.empty((nq, kk, mm), np.float32)
+            gkeys = np.empty((nq, kk), np.int64)
+            rcounts = np.empty((nq, kk), np.int32)
+            gsizes = np.empty((nq, kk), np.int64)
+            counts = np.empty(nq, np.int32)
+        p = self.params(flat_engine=flat_engine)
+        self._keep["group_rows"] = (queries,)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_group_rows(self.h, _ptr(queries), nq, k, m, C.byref(p), engine, int(page_rows), int(scratch_bytes),
+                                                       _ptr(ids), _ptr(dist), _ptr(gkeys), _ptr(rcounts), _ptr(gsizes), _ptr(counts)))
+        return ids, dist, gkeys, rcounts, gsizes, counts
+
     def groups_info(self):
         """eps_index_groups_info: {"n_groups", "largest_group", "last_engines": the engines the last search_groups ran, as names, "last_scan_queries"}"""
         g, big, scanned, engines = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
