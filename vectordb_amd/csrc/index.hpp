@@ -16,6 +16,7 @@
 
 #include "../../include/epsilla_gfx950.h"
 #include "kernels.hpp"
+#include "result_block.hpp"
 
 namespace eps {
 
@@ -213,10 +214,10 @@ class Index : public IndexBase {
   bool rows_owned_ = false;
   int64_t n_rows_ = 0;
   int64_t rows_version_ = 0;  // bumped on attach/append (invalidates the fp16 mirror)
-  // FLAT_AUTO, single-query traffic on a table without a mirror: calls seen on this rows version (flat_mfma_profitable: after a few of
-  // them the 8-bit mirror is worth its HBM - the one-pass search answers such a call in a third of the stream scan's time)
-  mutable int64_t small_calls_version_ = -1;
-  mutable int small_calls_ = 0;
+  // FLAT_AUTO, single-query traffic on a table without a mirror: searches seen on this rows version (flat_mfma_profitable with count_call:
+  // after a few of them the 8-bit mirror is worth its HBM - the one-pass search answers such a call in a third of the stream scan's time)
+  int64_t small_calls_version_ = -1;
+  int small_calls_ = 0;
   int64_t scan_limit_ = -1;   // >= 0: flat engines scan rows [0, scan_limit_) only (graph build over a prefix)
 
   int64_t id_base_ = 0, id_stride_ = 1;
@@ -247,7 +248,9 @@ class Index : public IndexBase {
   HalfMirror* mirror_ = nullptr;
 
   // scratch
-  DevBuf q_buf_, partial_buf_, run_buf_, out_buf_, tmp_buf_, page_buf_;   // out_buf_: [ids | distances | counts] of a call with host result pointers
+  // out_block_: the result block of whichever call with host result pointers is running (ResultBlock, result_block.hpp: every such call ends in
+  // a stream sync and the calls of one index follow one another, so one buffer serves them all)
+  DevBuf q_buf_, partial_buf_, run_buf_, out_block_, tmp_buf_, page_buf_;
   // r5: that block goes to the host in ONE copy into page-locked memory and is split there (three pageable device-to-host copies staged separately
   // cost a batch of 1024 ~0.1 ms and a single-vector call three trips through the DMA queue)
   struct HostBuf {
@@ -255,19 +258,23 @@ class Index : public IndexBase {
     size_t cap = 0;
     ~HostBuf();
     bool reserve(size_t bytes);
-  } h_out_, h_q_, h_rng_, h_among_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
-  DevBuf sel_bits_, sel_scan_, sel_out_;   // select(): visibility bitset; block counts | offsets; [count | total | ids] of a call with host result pointers
+  } h_out_, h_q_, h_rng_, h_evals_;   // (h_q_: host queries are copied to page-locked memory first, then DMA'd: the runtime's own path for pageable sources is slower)
+  DevBuf sel_bits_, sel_scan_;   // select(): visibility bitset; block counts | offsets
   // search_range(): survivor keys [nq][cap]; survivor counts | status | candidates re-ranked (what the host reads back); radii | fall-back query
-  // numbers; [ids | distances | counts | totals] of a call with host result pointers.  h_rng_: the page-locked side of the middle two
-  DevBuf rng_keys_, rng_cnt_, rng_in_, rng_out_;
-  // search_among(): [pair counter | offsets | a host list's ids].  h_among_: the counter's page-locked copy - the call's dist_evals, read by
-  // last_stats once the call's last event has passed (among_evals_pending_), so that a call with device results stays asynchronous
+  // numbers.  h_rng_: the page-locked side of the last two
+  DevBuf rng_keys_, rng_cnt_, rng_in_;
+  // search_among(): [pair counter | offsets | a host list's ids]
   DevBuf among_in_;
-  bool among_evals_pending_ = false;
+  // search_among(), search_group_rows(): the pairs given a distance are counted on the device.  h_evals_: the counter's page-locked copy - the
+  // call's dist_evals, read by last_stats once the call's last event has passed (evals_pending_), so that a call with device results stays
+  // asynchronous
+  bool evals_pending_ = false;
+  int32_t clear_device_evals(unsigned long long* d_evals);           // in front of the kernels that count
+  int32_t publish_device_evals(const unsigned long long* d_evals);   // behind them, in front of the call's last event
   // set_groups(): label[n] | key_of_label[G], valid for the table of (grp_version_, grp_rows_).  search_groups(): a page of keys [nq][P]; the
-  // result keys [nq][k]; [lo | compacted lo | counts | status | query numbers]; the compacted queries; the scan's table, its merged lists and
-  // [ids | group keys | distances | counts] of a call with host result pointers.  h_grp_: the word the compaction leaves the host
-  DevBuf grp_label_, grp_keys_, grp_page_, grp_res_, grp_state_, grp_q_, grp_table_, grp_run_, grp_out_;
+  // result keys [nq][k]; [lo | compacted lo | counts | status | query numbers]; the compacted queries; the scan's table and its merged lists.
+  // h_grp_: the word the compaction leaves the host
+  DevBuf grp_label_, grp_keys_, grp_page_, grp_res_, grp_state_, grp_q_, grp_table_, grp_run_;
   HostBuf h_grp_;
   int64_t grp_n_groups_ = 0, grp_largest_ = 0, grp_rows_ = -1, grp_version_ = -1, grp_last_scan_queries_ = 0;
   int32_t grp_last_engines_ = 0;
@@ -297,6 +304,12 @@ class Index : public IndexBase {
   int64_t fcol_rows_ = 0;       // rows the attribute column behind d_fcol_ covers
 
   eps_search_stats stats_{};
+  void set_main_kernel(int64_t launches, int64_t rows, int64_t queries, int32_t bits) {   // the launch a call reports as its main kernel
+    stats_.main_kernel_launches = launches;
+    stats_.main_kernel_rows = rows;
+    stats_.main_kernel_queries = queries;
+    stats_.main_kernel_bits = bits;
+  }
   // what search() publishes to the matrix engine for the length of one call (cleared by `call_ = {}` on every way out of it)
   struct CallCtx {
     // what the engine launches right before its final host sync (the result conversion), so that the device works through the round trip;
@@ -316,7 +329,15 @@ class Index : public IndexBase {
   int32_t flat_stream(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric = -1, bool filtered = true);
   int32_t flat_stream_page(const float* dq, int64_t nq, int k, int64_t row_begin, int64_t row_end, u64* run_keys, int metric, bool filtered,
                            const u64* lo, int64_t lo_stride);
-  // ---- the steps search, select and search_range share (index_calls.cpp)
+  // ---- the steps the serving calls share (index_calls.cpp)
+  // the flat engine a call of (nq, k) takes for eps_search_params::flat_engine: the matrix engine (MFMA and MFMA_I8 as asked, AUTO where
+  // flat_mfma_profitable) or the stream engine, and the matrix engine's operand width (0: the library's choice).  counts_towards_mirror: an AUTO
+  // call with few queries counts towards building the 8-bit mirror - a search's business only.  known false: no such engine
+  struct FlatChoice {
+    bool known, matrix;
+    int bits;
+  };
+  FlatChoice resolve_flat_engine(int flat_engine, int64_t nq, int k, bool counts_towards_mirror);
   // refuses a deleted bitset / filter column / filter program's rows that an append has left shorter than the table
   int32_t check_filters_cover_table(const char* who);
   // a call that reports statistics and takes a slot of the kernel ring (select takes neither: it leaves no trace)
@@ -328,12 +349,8 @@ class Index : public IndexBase {
   int32_t copy_host_in(void* dst, const void* src, size_t bytes, bool call_syncs);
   // *dq = queries where they are on the device already, else their upload in q_buf_ (call_syncs: see copy_host_in)
   int32_t stage_queries(const char* who, const float* queries, int64_t nq, const float** dq, bool call_syncs);
-  // one device block of results to up to four host arrays: part i is `bytes` bytes at `off` of the block (dst null: not asked for)
-  struct HostPart {
-    void* dst;
-    size_t off, bytes;
-  };
-  int32_t fetch_to_host(const void* d_block, size_t block_bytes, std::initializer_list<HostPart> parts);
+  // a host call's result block to the caller's arrays (the parts asked for), and the stream sync that ends the call
+  int32_t fetch_to_host(const ResultBlock& rb);
   friend int32_t quant8_view(Index&, Quant8View*);
   friend void quant8_queries(Index&, const Quant8View&, const float*, int64_t, signed char*, float*);
   friend int32_t one_pass_probe(Index&, const float*, int64_t, int, eps_one_pass_form*, u32*, u64*, int32_t*, float*, int32_t*, int32_t*);
@@ -420,7 +437,8 @@ class SparseIndex {
 int32_t flat_mfma_search(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool approx = false, int bits = 0);
 int32_t flat_mfma_search_slice(Index& ix, const float* dq, int64_t nq, int k, u64* run_keys, bool approx, int cap_scale = 1, int bits = 16,
                                bool auto_bits = false);  // <= 2048 queries
-bool flat_mfma_profitable(const Index& ix, int64_t nq, int k);  // AUTO heuristic
+// AUTO heuristic.  count_call: a single-query call on a table without a mirror counts towards building one (Index::small_calls_)
+bool flat_mfma_profitable(Index& ix, int64_t nq, int k, bool count_call);
 // stage-level entries of the flat matrix engine (eps_index_mirror_view / eps_index_filter_pass): host arrays, no side effects a search could see
 int32_t flat_mirror_view(Index& ix, int bits, const float* queries, int64_t nq, eps_mirror_view* v);
 int32_t flat_filter_pass(Index& ix, const float* queries, int64_t nq, int bits, int64_t lo, int64_t hi, int64_t cap, int mode, int thr_form, const void* thr,
@@ -463,6 +481,12 @@ inline eps_build_params build_params_or_default(const eps_build_params* p) {
   if (p) bp = *p; else eps_default_build_params(&bp);
   return bp;
 }
+inline eps_search_params search_params_or_default(const eps_search_params* p) {
+  eps_search_params sp;
+  if (p) sp = *p; else eps_default_search_params(&sp);
+  return sp;
+}
+inline bool flat_engine_known(int flat_engine) { return flat_engine >= EPS_FLAT_AUTO && flat_engine <= EPS_FLAT_MFMA_I8; }
 
 // for member functions of Index that return a status
 #define HIP_TRY(expr)                                  \

@@ -1,9 +1,8 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, the steps they share, and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, the steps they share (their results: result_block.hpp), and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -77,7 +76,7 @@ int32_t Index::check_filters_cover_table(const char* who) {
 void Index::begin_timed_call() {
   std::memset(&stats_, 0, sizeof(stats_));
   stage_n_ = 0;
-  among_evals_pending_ = false;
+  evals_pending_ = false;
   kring_seq_ += 1;
   const int slot = (int)(kring_seq_ % KRING);
   evk0_ = kring_[slot][0];
@@ -112,25 +111,42 @@ int32_t Index::stage_queries(const char* who, const float* queries, int64_t nq, 
   return EPS_OK;
 }
 
-int32_t Index::fetch_to_host(const void* d_block, size_t block_bytes, std::initializer_list<HostPart> parts) {
-  if (!(tune_int("EPS_HOST_STAGING", 1) == 0) && h_out_.reserve(block_bytes)) {   // one copy into page-locked memory, split on the host
-    HIP_TRY(hipMemcpyAsync(h_out_.p, d_block, block_bytes, hipMemcpyDeviceToHost, stream_));
+int32_t Index::fetch_to_host(const ResultBlock& rb) {
+  if (!(tune_int("EPS_HOST_STAGING", 1) == 0) && h_out_.reserve(rb.bytes())) {   // one copy into page-locked memory, split on the host
+    HIP_TRY(hipMemcpyAsync(h_out_.p, rb.block(), rb.bytes(), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    for (const HostPart& part : parts)
-      if (part.dst) memcpy(part.dst, static_cast<const char*>(h_out_.p) + part.off, part.bytes);
+    rb.split(h_out_.p);
   } else {   // (no page-locked memory to be had: the pageable copies)
-    for (const HostPart& part : parts)
-      if (part.dst) HIP_TRY(hipMemcpyAsync(part.dst, static_cast<const char*>(d_block) + part.off, part.bytes, hipMemcpyDeviceToHost, stream_));
+    for (int i = 0; i < rb.size(); ++i) {
+      const ResultBlock::Part& part = rb.part(i);
+      if (part.dst) HIP_TRY(hipMemcpyAsync(part.dst, static_cast<const char*>(rb.block()) + part.off, part.bytes, hipMemcpyDeviceToHost, stream_));
+    }
     HIP_TRY(hipStreamSynchronize(stream_));
   }
+  return EPS_OK;
+}
+
+Index::FlatChoice Index::resolve_flat_engine(int flat_engine, int64_t nq, int k, bool counts_towards_mirror) {
+  if (!flat_engine_known(flat_engine)) return FlatChoice{false, false, 0};
+  const int bits = flat_engine == EPS_FLAT_MFMA ? 16 : (flat_engine == EPS_FLAT_MFMA_I8 ? 8 : 0);   // AUTO: the library picks the operand width too
+  const bool matrix = flat_engine == EPS_FLAT_AUTO ? flat_mfma_profitable(*this, nq, k, counts_towards_mirror) : flat_engine != EPS_FLAT_STREAM;
+  return FlatChoice{true, matrix, bits};
+}
+
+int32_t Index::clear_device_evals(unsigned long long* d_evals) {
+  HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
+  return EPS_OK;
+}
+int32_t Index::publish_device_evals(const unsigned long long* d_evals) {
+  HIP_TRY(hipMemcpyAsync(h_evals_.p, d_evals, 8, hipMemcpyDeviceToHost, stream_));
+  evals_pending_ = true;
   return EPS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ search
 int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_search_params* pp, int64_t* ids,
                       float* dist, int32_t* counts, int32_t walk_limit) {
-  eps_search_params p;
-  if (pp) p = *pp; else eps_default_search_params(&p);
+  const eps_search_params p = search_params_or_default(pp);
   prefilter_call_ = p.prefilter != 0;
   if (nq < 0 || k <= 0) return fail(EPS_USER_ERROR, "search: nq must be >= 0 and k > 0");
   if (nq == 0) return EPS_OK;
@@ -143,9 +159,12 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
   int32_t rc = check_filters_cover_table("search");
   if (rc != EPS_OK) return rc;
 
-  const bool out_dev = is_device_ptr(ids);
-  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)))
-    return fail(EPS_USER_ERROR, "search: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
 
   const float* dq;
   rc = stage_queries("search", queries, nq, &dq, !out_dev);   // (host results: fetch_to_host ends the call in a sync)
@@ -172,16 +191,10 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
 
   // results out (decided before the engines run: the matrix engine launches the result conversion itself, in front of its final
   // host sync, so that the device does not idle through that round trip)
-  int64_t* d_ids = ids;
-  float* d_dist = dist;
-  int32_t* d_cnt = counts;
-  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float), out_bytes = ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
-  if (!out_dev) {
-    if (!out_buf_.reserve(out_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (outputs)");
-    d_ids = out_buf_.as<int64_t>();
-    d_dist = reinterpret_cast<float*>(out_buf_.as<char>() + ids_bytes);
-    d_cnt = reinterpret_cast<int32_t*>(out_buf_.as<char>() + ids_bytes + dist_bytes);
-  }
+  if (!rb.place(out_block_)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory (outputs)");
+  int64_t* const d_ids = rb.dev(r_ids);
+  float* const d_dist = rb.dev(r_dist);
+  int32_t* const d_cnt = rb.dev(r_cnt);
   result_finalized_ = false;
   auto finalize = [&]() {
     launch_finalize(run_keys, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
@@ -193,17 +206,16 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
   if (mode == EPS_MODE_FLAT) {
     if (cap_local && p.local_queue < keff) keff = (int)p.local_queue;
     if (keff < k) launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
-    int engine = p.flat_engine;
-    if (engine < EPS_FLAT_AUTO || engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search: unknown flat engine");
-    int bits = engine == EPS_FLAT_MFMA ? 16 : (engine == EPS_FLAT_MFMA_I8 ? 8 : 0);   // AUTO: the library picks the operand width too
-    if (engine == EPS_FLAT_MFMA_I8) engine = EPS_FLAT_MFMA;
-    if (engine == EPS_FLAT_AUTO) engine = flat_mfma_profitable(*this, nq, keff) ? EPS_FLAT_MFMA : EPS_FLAT_STREAM;
+    const FlatChoice fc = resolve_flat_engine(p.flat_engine, nq, keff, true);
+    if (!fc.known) return fail(EPS_USER_ERROR, "search: unknown flat engine");
+    bool matrix = fc.matrix;
+    const int bits = fc.bits;
     // a filter on @distance needs exact distances wherever it is evaluated; the MFMA engine selects its seeds on
     // approximate keys, so such searches stay on the exact stream engine
-    if (prog_len_ > 0 && prog_uses_dist_ && !prefilter_call_) engine = EPS_FLAT_STREAM;
-    if (keff > 1024) engine = EPS_FLAT_STREAM;   // result pages (see flat_stream)
+    if (prog_len_ > 0 && prog_uses_dist_ && !prefilter_call_) matrix = false;
+    if (keff > 1024) matrix = false;   // result pages (see flat_stream)
     if (keff == k) {
-      if (engine == EPS_FLAT_MFMA) {
+      if (matrix) {
         // (called by the engine in front of its final sync; again after a fall-back pass.  The callable captures locals of this
         // frame: the guard clears it on every way out, an exception from the engine included)
         struct CallGuard {
@@ -219,8 +231,7 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
       // narrower result (L_local cap): compute into a k_eff-wide list, then widen
       if (!tmp_buf_.reserve((size_t)nq * keff * sizeof(u64))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search: out of device memory");
       u64* narrow = tmp_buf_.as<u64>();
-      rc = engine == EPS_FLAT_MFMA ? flat_mfma_search(*this, dq, nq, keff, narrow, false, bits)
-                                   : flat_stream(dq, nq, keff, 0, n_rows_, narrow);
+      rc = matrix ? flat_mfma_search(*this, dq, nq, keff, narrow, false, bits) : flat_stream(dq, nq, keff, 0, n_rows_, narrow);
       if (rc == EPS_OK)
         HIP_TRY(hipMemcpy2DAsync(run_keys, (size_t)k * sizeof(u64), narrow, (size_t)keff * sizeof(u64),
                                  (size_t)keff * sizeof(u64), (size_t)nq, hipMemcpyDeviceToDevice, stream_));
@@ -234,7 +245,7 @@ int32_t Index::search(const float* queries, int64_t nq, int32_t k, const eps_sea
 
   if (!result_finalized_) finalize();
   if (!out_dev) {
-    rc = fetch_to_host(d_ids, out_bytes, {{ids, 0, ids_bytes}, {dist, ids_bytes, dist_bytes}, {counts, ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    rc = fetch_to_host(rb);
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
@@ -252,9 +263,13 @@ int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* co
   const int32_t rc = check_filters_cover_table("select");
   if (rc != EPS_OK) return rc;
   const int64_t n = n_rows_;
-  const bool out_dev = is_device_ptr(count_out);
-  if ((limit > 0 && n > 0 && out_dev != is_device_ptr(ids_out)) || (total_out && out_dev != is_device_ptr(total_out)))
-    return fail(EPS_USER_ERROR, "select: ids_out, count_out and total_out must all be host or all be device pointers");
+  // [count | total | ids]: the head a host call reads first.  (Where no id can be written - limit 0, no rows - ids_out is not looked at)
+  ResultBlock rb;
+  const auto r_count = rb.add(count_out, 1);
+  const auto r_total = rb.add(total_out, 1);
+  const auto r_ids = rb.add(limit > 0 && n > 0 ? ids_out : nullptr, (size_t)std::min(limit, n));
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "select: ids_out, count_out and total_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
   if (n == 0) {   // an empty table: nothing to judge
     if (out_dev) {
       HIP_TRY(hipMemsetAsync(count_out, 0, sizeof(int64_t), stream_));
@@ -276,19 +291,19 @@ int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* co
   const int64_t nblocks = select_blocks(n);
   const size_t counts_bytes = ((size_t)nblocks * sizeof(u32) + 7) & ~(size_t)7;
   if (!sel_bits_.reserve((size_t)nblocks * (SEL_ROWS / 8)) || !sel_scan_.reserve(counts_bytes + (size_t)(nblocks + 1) * sizeof(int64_t)) ||
-      (!out_dev && !sel_out_.reserve((size_t)(2 + a.limit) * sizeof(int64_t))))
+      !rb.place(out_block_))
     return fail(EPS_INFRA_UNEXPECTED_ERROR, "select: out of device memory (scratch)");
   a.bits = sel_bits_.as<u64>();
   a.counts = sel_scan_.as<u32>();
   a.offsets = reinterpret_cast<int64_t*>(sel_scan_.as<char>() + counts_bytes);
-  a.ids_out = out_dev ? ids_out : sel_out_.as<int64_t>() + 2;
-  a.count_out = out_dev ? count_out : sel_out_.as<int64_t>();
-  a.total_out = out_dev ? total_out : sel_out_.as<int64_t>() + 1;
+  a.ids_out = rb.dev(r_ids);
+  a.count_out = rb.dev(r_count);
+  a.total_out = rb.dev(r_total);
   launch_select(a, stream_);
   HIP_TRY(hipGetLastError());
-  if (!out_dev) {   // count and total first: only the ids of the window cross PCIe, not `limit` slots
+  if (!out_dev) {   // count and total first (the block's first two parts: 16 bytes): only the ids of the window cross PCIe, not `limit` slots
     int64_t head[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(head, sel_out_.p, sizeof(head), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(head, rb.block(), sizeof(head), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     if (head[0] > 0) {
       HIP_TRY(hipMemcpyAsync(ids_out, a.ids_out, (size_t)head[0] * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
@@ -309,21 +324,24 @@ int32_t Index::select(int64_t skip, int64_t limit, int64_t* ids_out, int64_t* co
 // Reports like a search (statistics, kernel ring); changes nothing a later search can observe.
 int32_t Index::search_range(const float* queries, int64_t nq, const float* radius, int32_t cap, const eps_search_params* pp, int64_t* ids, float* dist,
                             int32_t* counts, int64_t* totals) {
-  eps_search_params p;
-  if (pp) p = *pp; else eps_default_search_params(&p);
+  const eps_search_params p = search_params_or_default(pp);
   if (nq < 0) return fail(EPS_USER_ERROR, "search_range: nq must be >= 0");
   if (cap < 1 || cap > RANGE_MAX_CAP) return fail(EPS_USER_ERROR, "search_range: cap must be in [1, 8192]");
   if (nq == 0) return EPS_OK;
   if (!queries || !radius || !ids || !dist) return fail(EPS_USER_ERROR, "search_range: null buffer");
-  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_range: unknown flat engine");
+  if (!flat_engine_known(p.flat_engine)) return fail(EPS_USER_ERROR, "search_range: unknown flat engine");
   HIP_TRY(hipSetDevice(device_));
   if (is_device_ptr(radius)) return fail(EPS_USER_ERROR, "search_range: radius must be a host array");
   for (int64_t j = 0; j < nq; ++j)
     if (radius[j] != radius[j]) return fail(EPS_USER_ERROR, "search_range: a radius is NaN");
   int32_t rc = check_filters_cover_table("search_range");
   if (rc != EPS_OK) return rc;
-  const bool out_dev = is_device_ptr(ids);
-  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)) || (totals && out_dev != is_device_ptr(totals)))
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * cap);
+  const auto r_totals = rb.add(totals, (size_t)nq);
+  const auto r_dist = rb.add(dist, (size_t)nq * cap);
+  const auto r_counts = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr))
     return fail(EPS_USER_ERROR, "search_range: ids_out, dist_out, counts_out and totals_out must all be host or all be device pointers");
   begin_timed_call();
   prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
@@ -331,10 +349,7 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
 
   // ---- scratch.  Device: [counts | status | candidates re-ranked], [radii | fall-back query numbers]; page-locked: [radii | read-back | query numbers]
   const size_t rb_bytes = (((size_t)nq * 8 + 7) & ~(size_t)7) + 8, rad_bytes = ((size_t)nq * 4 + 7) & ~(size_t)7;
-  const size_t ids_bytes = (size_t)nq * cap * sizeof(int64_t), tot_bytes = (size_t)nq * sizeof(int64_t), dist_bytes = (size_t)nq * cap * sizeof(float);
-  const size_t out_bytes = ids_bytes + tot_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
-  if (!rng_keys_.reserve((size_t)nq * cap * sizeof(u64)) || !rng_cnt_.reserve(rb_bytes) || !rng_in_.reserve(2 * rad_bytes) ||
-      (!out_dev && !rng_out_.reserve(out_bytes)))
+  if (!rng_keys_.reserve((size_t)nq * cap * sizeof(u64)) || !rng_cnt_.reserve(rb_bytes) || !rng_in_.reserve(2 * rad_bytes) || !rb.place(out_block_))
     return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of device memory (scratch)");
   if (!h_rng_.reserve(2 * rad_bytes + rb_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_range: out of page-locked host memory");
   float* h_rad = static_cast<float*>(h_rng_.p);
@@ -356,16 +371,6 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
 
   const RangeLists L{rng_keys_.as<u64>(), d_cnt, rng_in_.as<float>(), cap};
   const FilterSpec fs = filter_spec();
-  int64_t* d_ids = ids;
-  float* d_dist = dist;
-  int32_t* d_counts = counts;
-  int64_t* d_totals = totals;
-  if (!out_dev) {
-    d_ids = rng_out_.as<int64_t>();
-    d_totals = reinterpret_cast<int64_t*>(rng_out_.as<char>() + ids_bytes);
-    d_dist = reinterpret_cast<float*>(rng_out_.as<char>() + ids_bytes + tot_bytes);
-    d_counts = reinterpret_cast<int32_t*>(rng_out_.as<char>() + ids_bytes + tot_bytes + dist_bytes);
-  }
   // the stream form over the `m` queries named by sel (null: all of them), in launches of at most 32768 queries (the grid's y extent)
   auto scan = [&](const int32_t* sel, int64_t m) {
     for (int64_t q0 = 0; q0 < m; q0 += 32768) {
@@ -379,7 +384,7 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
     stats_.dist_evals += m * n;
   };
   auto order = [&](const int32_t* sel, int64_t m, const u64* topk) {
-    launch_range_order(RangeOrderArgs{m, sel, L, topk, d_status, id_base_, id_stride_, d_ids, d_dist, d_counts, d_totals}, stream_);
+    launch_range_order(RangeOrderArgs{m, sel, L, topk, d_status, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_counts), rb.dev(r_totals)}, stream_);
   };
   auto read_back = [&]() -> hipError_t {
     const hipError_t er = hipMemcpyAsync(h_rb, rng_cnt_.p, rb_bytes, hipMemcpyDeviceToHost, stream_);   // (status and totals only: the results cross PCIe once, at the end)
@@ -395,28 +400,17 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
   };
 
   // ---- the pass
-  int engine = p.flat_engine;
-  bool matrix = engine == EPS_FLAT_MFMA || engine == EPS_FLAT_MFMA_I8;
-  if (engine == EPS_FLAT_AUTO) {   // (the rule counts single-query calls towards building a mirror: that is a search's business)
-    const int64_t keep_version = small_calls_version_;
-    const int keep_calls = small_calls_;
-    matrix = flat_mfma_profitable(*this, nq, 1);
-    small_calls_version_ = keep_version;
-    small_calls_ = keep_calls;
-  }
+  const FlatChoice fc = resolve_flat_engine(p.flat_engine, nq, 1, false);   // (a filter on @distance too: the exact tail evaluates it)
   bool served = false;
-  if (matrix) {
-    rc = flat_range_lists(*this, dq, nq, engine == EPS_FLAT_MFMA ? 16 : (engine == EPS_FLAT_MFMA_I8 ? 8 : 0), L, d_cand_total, &served);
+  if (fc.matrix) {
+    rc = flat_range_lists(*this, dq, nq, fc.bits, L, d_cand_total, &served);
     if (rc != EPS_OK) return rc;
   }
   if (!served && n > 0) {
     HIP_TRY(hipEventRecord(evk0_, stream_));
     scan(nullptr, nq);
     HIP_TRY(hipEventRecord(evk1_, stream_));
-    stats_.main_kernel_launches = 1;
-    stats_.main_kernel_rows = n;
-    stats_.main_kernel_queries = nq;
-    stats_.main_kernel_bits = 32;
+    set_main_kernel(1, n, nq, 32);
   }
   order(nullptr, nq, nullptr);
   HIP_TRY(hipGetLastError());
@@ -458,17 +452,12 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
     order(d_sel, m, run_buf_.as<u64>());
     HIP_TRY(hipGetLastError());
   }
-  if (fell_back > 0) {   // the call's main kernel stays the pass
-    stats_.main_kernel_launches = pass_stats.main_kernel_launches;
-    stats_.main_kernel_rows = pass_stats.main_kernel_rows;
-    stats_.main_kernel_queries = pass_stats.main_kernel_queries;
-    stats_.main_kernel_bits = pass_stats.main_kernel_bits;
-  }
+  // the call's main kernel stays the pass
+  if (fell_back > 0) set_main_kernel(pass_stats.main_kernel_launches, pass_stats.main_kernel_rows, pass_stats.main_kernel_queries, pass_stats.main_kernel_bits);
   stats_.overflow_queries = fell_back;
   HIP_TRY(hipEventRecord(ev1_, stream_));
-  if (!out_dev) {
-    rc = fetch_to_host(rng_out_.p, out_bytes, {{ids, 0, ids_bytes}, {totals, ids_bytes, tot_bytes}, {dist, ids_bytes + tot_bytes, dist_bytes},
-                                               {counts, ids_bytes + tot_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+  if (!rb.device()) {
+    rc = fetch_to_host(rb);
     if (rc != EPS_OK) return rc;
   }
   end_timed_call();
@@ -489,9 +478,12 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   if (among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_among: ") + why);
   if (nq == 0) return EPS_OK;
   if (!queries || !ids || !dist || (n_cand > 0 && !cand_ids)) return fail(EPS_USER_ERROR, "search_among: null buffer");
-  const bool out_dev = is_device_ptr(ids);
-  if (out_dev != is_device_ptr(dist) || (counts && out_dev != is_device_ptr(counts)))
-    return fail(EPS_USER_ERROR, "search_among: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search_among: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
   int32_t rc = check_filters_cover_table("search_among");
   if (rc != EPS_OK) return rc;
   begin_timed_call();
@@ -505,15 +497,15 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   const bool ids_dev = n_cand > 0 && is_device_ptr(cand_ids);
   const size_t off_bytes = cand_offsets ? (size_t)(nq + 1) * sizeof(int64_t) : 0, list_bytes = ids_dev ? 0 : (size_t)n_cand * sizeof(int64_t);
   const AmongPlan plan = among_plan(!cand_offsets, nq, longest, k, pick_nq(nq, k, (int)dim_));
-  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float), out_bytes = ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
   if (!among_in_.reserve(8 + off_bytes + list_bytes) || !partial_buf_.reserve((size_t)nq * plan.W * k * sizeof(u64)) ||
-      !run_buf_.reserve((size_t)nq * k * sizeof(u64)) || (!out_dev && !out_buf_.reserve(out_bytes)))
+      !run_buf_.reserve((size_t)nq * k * sizeof(u64)) || !rb.place(out_block_))
     return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of device memory (scratch)");
-  if (!h_among_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of page-locked host memory");
+  if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of page-locked host memory");
   unsigned long long* d_evals = among_in_.as<unsigned long long>();
   int64_t* d_off = cand_offsets ? among_in_.as<int64_t>() + 1 : nullptr;
   const int64_t* d_list = cand_ids;
-  HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
+  rc = clear_device_evals(d_evals);
+  if (rc != EPS_OK) return rc;
   if (cand_offsets) {
     rc = copy_host_in(d_off, cand_offsets, off_bytes, !out_dev);
     if (rc != EPS_OK) return rc;
@@ -524,20 +516,11 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
     if (rc != EPS_OK) return rc;
   }
   u64* run_keys = run_buf_.as<u64>();
-  int64_t* d_ids = ids;
-  float* d_dist = dist;
-  int32_t* d_cnt = counts;
-  if (!out_dev) {
-    d_ids = out_buf_.as<int64_t>();
-    d_dist = reinterpret_cast<float*>(out_buf_.as<char>() + ids_bytes);
-    d_cnt = reinterpret_cast<int32_t*>(out_buf_.as<char>() + ids_bytes + dist_bytes);
-  }
   HIP_TRY(hipEventRecord(ev0_, stream_));
 
-  stats_.main_kernel_rows = n_cand;
-  stats_.main_kernel_queries = nq;
-  stats_.main_kernel_bits = 32;
-  if (n_cand > 0 && n_rows_ > 0) {
+  const bool any = n_cand > 0 && n_rows_ > 0;   // (else no list entry can name a row)
+  set_main_kernel(any ? 1 : 0, n_cand, nq, 32);
+  if (any) {
     AmongArgs a;
     a.rows = d_rows_;
     a.n_rows = n_rows_;
@@ -559,16 +542,15 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
     launch_among_gather(a, stream_);
     HIP_TRY(hipEventRecord(evk1_, stream_));
     launch_among_merge(a.partial, plan.W, k, nq, run_keys, stream_);
-    stats_.main_kernel_launches = 1;
-  } else {   // no list entry can name a row
+  } else {
     launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
   }
-  launch_finalize(run_keys, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
-  HIP_TRY(hipMemcpyAsync(h_among_.p, d_evals, 8, hipMemcpyDeviceToHost, stream_));
-  among_evals_pending_ = true;
+  launch_finalize(run_keys, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_cnt), stream_);
+  rc = publish_device_evals(d_evals);
+  if (rc != EPS_OK) return rc;
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {
-    rc = fetch_to_host(d_ids, out_bytes, {{ids, 0, ids_bytes}, {dist, ids_bytes, dist_bytes}, {counts, ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    rc = fetch_to_host(rb);
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
@@ -624,19 +606,23 @@ int32_t Index::groups_info(int64_t* n_groups, int64_t* largest_group, int32_t* l
 // Reports like a search (statistics, kernel ring); changes nothing a later search can observe.
 int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const eps_search_params* pp, int32_t engine, int32_t page_rows, int64_t scratch_bytes,
                              int64_t* ids, float* dist, int64_t* group_keys, int32_t* counts) {
-  eps_search_params p;
-  if (pp) p = *pp; else eps_default_search_params(&p);
+  const eps_search_params p = search_params_or_default(pp);
   const char* why;
   if (groups_args_check(nq, k, engine, page_rows, scratch_bytes, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_groups: ") + why);
-  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_groups: unknown flat engine");
+  if (!flat_engine_known(p.flat_engine)) return fail(EPS_USER_ERROR, "search_groups: unknown flat engine");
   if (nq == 0) return EPS_OK;
   HIP_TRY(hipSetDevice(device_));
   int32_t rc = groups_ready("search_groups");
   if (rc != EPS_OK) return rc;
   if (!queries || !ids || !dist || !group_keys) return fail(EPS_USER_ERROR, "search_groups: null buffer");
-  const bool out_dev = is_device_ptr(ids);
-  if (out_dev != is_device_ptr(dist) || out_dev != is_device_ptr(group_keys) || (counts && out_dev != is_device_ptr(counts)))
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_gk = rb.add(group_keys, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr))
     return fail(EPS_USER_ERROR, "search_groups: ids_out, dist_out, group_keys_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
   rc = check_filters_cover_table("search_groups");
   if (rc != EPS_OK) return rc;
   begin_timed_call();
@@ -645,28 +631,15 @@ int32_t Index::search_groups(const float* queries, int64_t nq, int32_t k, const 
   const float* dq;
   rc = stage_queries("search_groups", queries, nq, &dq, !out_dev);
   if (rc != EPS_OK) return rc;
-  const size_t ids_bytes = (size_t)nq * k * sizeof(int64_t), dist_bytes = (size_t)nq * k * sizeof(float);
-  const size_t out_bytes = 2 * ids_bytes + dist_bytes + (size_t)nq * sizeof(int32_t);
-  if (!out_dev && !grp_out_.reserve(out_bytes)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (scratch)");
-  int64_t* d_ids = ids;
-  int64_t* d_gk = group_keys;
-  float* d_dist = dist;
-  int32_t* d_cnt = counts;
-  if (!out_dev) {
-    d_ids = grp_out_.as<int64_t>();
-    d_gk = reinterpret_cast<int64_t*>(grp_out_.as<char>() + ids_bytes);
-    d_dist = reinterpret_cast<float*>(grp_out_.as<char>() + 2 * ids_bytes);
-    d_cnt = reinterpret_cast<int32_t*>(grp_out_.as<char>() + 2 * ids_bytes + dist_bytes);
-  }
+  if (!rb.place(out_block_)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_groups: out of device memory (scratch)");
   rc = groups_representatives("search_groups", dq, nq, k, p, engine, page_rows, scratch_bytes);
   if (rc != EPS_OK) return rc;
   const u64* res = grp_res_.as<u64>();
-  launch_finalize(res, nq, k, id_base_, id_stride_, d_ids, d_dist, d_cnt, stream_);
-  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), d_gk, stream_);
+  launch_finalize(res, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_cnt), stream_);
+  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), rb.dev(r_gk), stream_);
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {
-    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, ids_bytes, ids_bytes}, {dist, 2 * ids_bytes, dist_bytes},
-                                               {counts, 2 * ids_bytes + dist_bytes, (size_t)nq * sizeof(int32_t)}});
+    rc = fetch_to_host(rb);
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
@@ -707,18 +680,9 @@ int32_t Index::groups_representatives(const char* who, const float* dq, int64_t 
     u64* page = grp_page_.as<u64>();
     for (int round = 0; left > 0 && (engine == EPS_GROUPS_PAGES || round < GROUPS_AUTO_ROUNDS); ++round) {
       if (round == 0) {   // the flat engine a search of (nq, P) would take; all of them carry the stream scan's bits
-        int fe = p.flat_engine;
-        const int bits = fe == EPS_FLAT_MFMA ? 16 : (fe == EPS_FLAT_MFMA_I8 ? 8 : 0);
-        if (fe == EPS_FLAT_MFMA_I8) fe = EPS_FLAT_MFMA;
-        if (fe == EPS_FLAT_AUTO) {   // (the rule counts single-query calls towards building a mirror: that is a search's business)
-          const int64_t keep_version = small_calls_version_;
-          const int keep_calls = small_calls_;
-          fe = flat_mfma_profitable(*this, nq, P) ? EPS_FLAT_MFMA : EPS_FLAT_STREAM;
-          small_calls_version_ = keep_version;
-          small_calls_ = keep_calls;
-        }
-        if (prog_len_ > 0 && prog_uses_dist_) fe = EPS_FLAT_STREAM;   // (a filter on @distance needs exact distances where it is evaluated)
-        rc = fe == EPS_FLAT_MFMA ? flat_mfma_search(*this, dq, nq, P, page, false, bits) : flat_stream_page(dq, nq, P, 0, n, page, -1, true, nullptr, 0);
+        const FlatChoice fc = resolve_flat_engine(p.flat_engine, nq, P, false);   // (known: the callers have refused any other)
+        const bool matrix = fc.matrix && !(prog_len_ > 0 && prog_uses_dist_);   // (a filter on @distance needs exact distances where it is evaluated)
+        rc = matrix ? flat_mfma_search(*this, dq, nq, P, page, false, fc.bits) : flat_stream_page(dq, nq, P, 0, n, page, -1, true, nullptr, 0);
       } else {
         launch_groups_gather(dq, (int)dim_, d_lo, d_qsel, left, grp_q_.as<float>(), d_clo, stream_);
         rc = flat_stream_page(grp_q_.as<float>(), left, P, 0, n, page, -1, true, d_clo, 1);
@@ -762,11 +726,8 @@ int32_t Index::groups_representatives(const char* who, const float* dq, int64_t 
       launch_groups_table_topk(best, G, mc, k, plan, partial_buf_.as<u64>(), stream_);
       launch_among_merge(partial_buf_.as<u64>(), plan.W, k, mc, grp_run_.as<u64>(), stream_);
       launch_groups_scatter(grp_run_.as<u64>(), k, a.qsel, mc, named ? res : res + i0 * k, stream_);
-      stats_.main_kernel_queries = mc;
+      set_main_kernel(1, n, mc, 32);   // (the last chunk's)
     }
-    stats_.main_kernel_launches = 1;
-    stats_.main_kernel_rows = n;
-    stats_.main_kernel_bits = 32;
     stats_.dist_evals += left * n;
     grp_last_engines_ |= 1 << EPS_GROUPS_SCAN;
     grp_last_scan_queries_ = left;
@@ -799,20 +760,25 @@ void Index::forget_rows_by_group() {
 int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* pp, int32_t engine, int32_t page_rows,
                                  int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* row_counts, int64_t* group_sizes,
                                  int32_t* counts) {
-  eps_search_params p;
-  if (pp) p = *pp; else eps_default_search_params(&p);
+  const eps_search_params p = search_params_or_default(pp);
   const char* why;
   if (group_rows_args_check(nq, k, m, engine, page_rows, scratch_bytes, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_group_rows: ") + why);
-  if (p.flat_engine < EPS_FLAT_AUTO || p.flat_engine > EPS_FLAT_MFMA_I8) return fail(EPS_USER_ERROR, "search_group_rows: unknown flat engine");
+  if (!flat_engine_known(p.flat_engine)) return fail(EPS_USER_ERROR, "search_group_rows: unknown flat engine");
   if (nq == 0) return EPS_OK;
   HIP_TRY(hipSetDevice(device_));
   int32_t rc = groups_ready("search_group_rows");
   if (rc != EPS_OK) return rc;
   if (!queries || !ids || !dist || !group_keys || !row_counts) return fail(EPS_USER_ERROR, "search_group_rows: null buffer");
-  const bool out_dev = is_device_ptr(ids);
-  if (out_dev != is_device_ptr(dist) || out_dev != is_device_ptr(group_keys) || out_dev != is_device_ptr(row_counts) ||
-      (group_sizes && out_dev != is_device_ptr(group_sizes)) || (counts && out_dev != is_device_ptr(counts)))
-    return fail(EPS_USER_ERROR, "search_group_rows: the output buffers must all be host or all be device pointers");
+  const size_t km = (size_t)k * m;
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * km);
+  const auto r_gk = rb.add(group_keys, (size_t)nq * k);
+  const auto r_gs = rb.add(group_sizes, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * km);
+  const auto r_rc = rb.add(row_counts, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search_group_rows: the output buffers must all be host or all be device pointers");
+  const bool out_dev = rb.device();
   rc = check_filters_cover_table("search_group_rows");
   if (rc != EPS_OK) return rc;
 
@@ -838,37 +804,22 @@ int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, in
 
   // ---- scratch: [pair counter | sizes | prefix] of a pass, its partial lists and merged lists; host results' device block
   const GroupRowsPlan plan = group_rows_plan(nq, k, m, n > 0 ? n : 1, grp_largest_ > 0 ? grp_largest_ : 1);
-  const int64_t km = (int64_t)k * m, pass_pairs = plan.slice * k;
-  const size_t ids_bytes = (size_t)nq * km * sizeof(int64_t), dist_bytes = (size_t)nq * km * sizeof(float), gk_bytes = (size_t)nq * k * sizeof(int64_t),
-               rc_bytes = (size_t)nq * k * sizeof(int32_t);
-  const size_t off_gk = ids_bytes, off_sizes = off_gk + gk_bytes, off_dist = off_sizes + gk_bytes, off_rc = off_dist + dist_bytes, off_cnt = off_rc + rc_bytes;
-  const size_t out_bytes = off_cnt + (size_t)nq * sizeof(int32_t);
+  const int64_t pass_pairs = plan.slice * k;
   if (!grp_work_.reserve(8 + (size_t)(2 * pass_pairs + 1) * sizeof(u32)) || !partial_buf_.reserve((size_t)plan.items * m * sizeof(u64)) ||
-      !grp_rows_run_.reserve((size_t)pass_pairs * m * sizeof(u64)) || (!out_dev && !grp_out_.reserve(out_bytes)))
+      !grp_rows_run_.reserve((size_t)pass_pairs * m * sizeof(u64)) || !rb.place(out_block_))
     return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of device memory (scratch)");
-  if (!h_among_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of page-locked host memory");
+  if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of page-locked host memory");
   unsigned long long* d_evals = grp_work_.as<unsigned long long>();
   u32* d_sizes = reinterpret_cast<u32*>(d_evals + 1);
-  int64_t* d_ids = ids;
-  int64_t* d_gk = group_keys;
-  int64_t* d_gs = group_sizes;
-  float* d_dist = dist;
-  int32_t* d_rc = row_counts;
-  int32_t* d_cnt = counts;
-  if (!out_dev) {
-    char* o = grp_out_.as<char>();
-    d_ids = reinterpret_cast<int64_t*>(o);
-    d_gk = reinterpret_cast<int64_t*>(o + off_gk);
-    d_gs = reinterpret_cast<int64_t*>(o + off_sizes);
-    d_dist = reinterpret_cast<float*>(o + off_dist);
-    d_rc = reinterpret_cast<int32_t*>(o + off_rc);
-    d_cnt = reinterpret_cast<int32_t*>(o + off_cnt);
-  }
+  // (device results: null where the caller passed null - group_sizes, counts - and the kernel skips them)
+  int64_t* const d_gs = rb.dev(r_gs);
+  int32_t* const d_cnt = rb.dev(r_cnt);
 
   rc = groups_representatives("search_group_rows", dq, nq, k, p, engine, page_rows, scratch_bytes);
   if (rc != EPS_OK) return rc;
   const u64* res = grp_res_.as<u64>();
-  HIP_TRY(hipMemsetAsync(d_evals, 0, 8, stream_));
+  rc = clear_device_evals(d_evals);
+  if (rc != EPS_OK) return rc;
   for (int64_t q0 = 0; q0 < nq; q0 += plan.slice) {
     GroupRowsArgs a;
     a.rows = d_rows_;
@@ -900,22 +851,16 @@ int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, in
     } else {   // no row: no group
       launch_fill_u64(a.run_keys, a.pairs * m, KEY_EMPTY, stream_);
     }
-    launch_group_rows_finalize(a, id_base_, id_stride_, d_ids + q0 * km, d_dist + q0 * km, d_rc + q0 * k, d_gs ? d_gs + q0 * k : nullptr,
-                               d_cnt ? d_cnt + q0 : nullptr, stream_);
+    launch_group_rows_finalize(a, id_base_, id_stride_, rb.dev(r_ids) + q0 * km, rb.dev(r_dist) + q0 * km, rb.dev(r_rc) + q0 * k,
+                               d_gs ? d_gs + q0 * k : nullptr, d_cnt ? d_cnt + q0 : nullptr, stream_);
   }
-  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), d_gk, stream_);
-  if (n > 0) {
-    stats_.main_kernel_launches = 1;
-    stats_.main_kernel_rows = n;
-    stats_.main_kernel_queries = nq;
-    stats_.main_kernel_bits = 32;
-  }
-  HIP_TRY(hipMemcpyAsync(h_among_.p, d_evals, 8, hipMemcpyDeviceToHost, stream_));   // (the second phase's pairs: last_stats adds them)
-  among_evals_pending_ = true;
+  launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), rb.dev(r_gk), stream_);
+  if (n > 0) set_main_kernel(1, n, nq, 32);
+  rc = publish_device_evals(d_evals);   // (the second phase's pairs: last_stats adds them)
+  if (rc != EPS_OK) return rc;
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {
-    rc = fetch_to_host(grp_out_.p, out_bytes, {{ids, 0, ids_bytes}, {group_keys, off_gk, gk_bytes}, {group_sizes, off_sizes, gk_bytes}, {dist, off_dist, dist_bytes},
-                                               {row_counts, off_rc, rc_bytes}, {counts, off_cnt, (size_t)nq * sizeof(int32_t)}});
+    rc = fetch_to_host(rb);
     if (rc != EPS_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
@@ -927,7 +872,7 @@ int32_t Index::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   // event timings are read lazily: the caller may have left the work in flight
   if (ev0_ && hipEventSynchronize(ev1_) == hipSuccess) {
-    if (among_evals_pending_) s.dist_evals += (int64_t)*static_cast<const unsigned long long*>(h_among_.p);   // (counted on the device, copied out in front of ev1_)
+    if (evals_pending_) s.dist_evals += (int64_t)*static_cast<const unsigned long long*>(h_evals_.p);   // (counted on the device, copied out in front of ev1_)
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) s.kernel_ms = ms;
     if (s.main_kernel_launches > 0 && hipEventElapsedTime(&ms, evk0_, evk1_) == hipSuccess) s.main_kernel_ms = ms;

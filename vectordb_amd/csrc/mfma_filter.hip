@@ -159,7 +159,7 @@ __global__ void stage_counts_kernel(const u32* cnt, int64_t nq, int cap, u32* ov
   atomicAdd(total, (unsigned long long)(c < (u32)cap ? c : (u32)cap));
 }
 
-bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
+bool flat_mfma_profitable(Index& ix, int64_t nq, int k, bool count_call) {
   // FLAT_AUTO: both engines return the same bits, so this is purely a cost decision.  The stream scan reads the fp32 rows once
   // per 4 queries; the filter reads its mirror once per <= 2048 queries - the 8-bit mirror is a quarter of the rows' bytes, the
   // fp16 mirror half - and pays ~20 small launches and one host sync per call (bench.py configs c2, 1M x 768, one query: stream
@@ -177,12 +177,16 @@ bool flat_mfma_profitable(const Index& ix, int64_t nq, int k) {
   const bool one_pass = one_pass_fits(ix, known8 && m->n8 == ix.n_rows_ ? m : nullptr, nq, k, ix.n_rows_);
   if (nq < 8 && !have8 && !have16) {
     // single-query traffic alone does not get a mirror (n x d bytes of HBM + a pass over the table to build it) at once: r4, after 16 such
-    // calls on the same rows it does, where the one-pass search can use it (0.20 ms instead of 0.62 ms per call at 1M x 768)
-    if (ix.small_calls_version_ != ix.rows_version_) {
+    // calls on the same rows it does, where the one-pass search can use it (0.20 ms instead of 0.62 ms per call at 1M x 768).  Only a call
+    // with count_call is such a call (a search); any other is judged as the next one would be and leaves the count as it is
+    if (count_call && ix.small_calls_version_ != ix.rows_version_) {
       ix.small_calls_version_ = ix.rows_version_;
       ix.small_calls_ = 0;
     }
-    if (!one_pass || known8 || ++ix.small_calls_ <= 16) return false;
+    if (!one_pass || known8) return false;
+    const int calls = (ix.small_calls_version_ == ix.rows_version_ ? ix.small_calls_ : 0) + 1;
+    if (count_call) ix.small_calls_ = calls;
+    if (calls <= 16) return false;
   }
   const bool use8 = have8 || !known8;                            // (an 8-bit mirror would be built first)
   const double rows = (double)ix.n_rows_, d = (double)ix.dim_;

@@ -376,26 +376,11 @@ class GpuIndex:
         """Returns (ids int64[nq,k], dist float32[nq,k], counts int32[nq]); numpy for host queries, or the
         caller-provided device tensors `out=(ids, dist, counts)`."""
         p = self.params(**kw)
-        if _is_dev(queries):
-            nq = queries.shape[0]
-            assert out is not None, "device queries need device output tensors: out=(ids, dist, counts)"
-            ids, dist, counts = out
-        else:
-            queries = np.ascontiguousarray(queries, np.float32)
-            if queries.ndim == 1:
-                queries = queries[None, :]
-            nq = queries.shape[0]
-            if out is not None:   # (host queries, caller-provided result buffers - host or device: the C ABI takes either side independently)
-                ids, dist, counts = out
-            else:
-                ids = np.empty((nq, k), np.int64)
-                dist = np.empty((nq, k), np.float32)
-                counts = np.empty(nq, np.int32)
-        assert queries.shape[1] == self.dim
-        if out is not None:   # the C ABI writes nq x k ids / distances and nq counts through raw pointers: the buffers must be what it assumes (ADVICE r5)
-            _check_out(ids, "ids", (nq, k), "int64")
-            _check_out(dist, "dist", (nq, k), "float32")
-            _check_out(counts, "counts", (nq,), "int32")
+        assert out is not None or not _is_dev(queries), "device queries need device output tensors: out=(ids, dist, counts)"
+        queries, nq = _queries_2d(queries, self.dim)
+        # (caller-provided buffers may be host or device whichever side the queries are on: the C ABI takes either, and refuses a mixed set itself)
+        ids, dist, counts = _results("search", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("counts", (nq,), "int32")), out, queries,
+                                     one_kind=False)
         self._check(self.L.eps_index_search(self.h, _ptr(queries), nq, k, C.byref(p), _ptr(ids), _ptr(dist), _ptr(counts)))
         return ids, dist, counts
 
@@ -427,28 +412,9 @@ class GpuIndex:
         the call is asynchronous on the index's stream.  out=(ids, dist, counts, totals): caller-provided buffers, all NumPy or all device."""
         engine = RANGE_ENGINES[flat_engine]
         cap = int(cap)
-        dev = _is_dev(queries)
-        if not dev:
-            queries = np.ascontiguousarray(queries, np.float32)
-            if queries.ndim == 1:
-                queries = queries[None, :]
-        nq = queries.shape[0]
-        assert queries.shape[1] == self.dim
+        queries, nq = _queries_2d(queries, self.dim)
         radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)))
-        if out is not None:
-            ids, dist, counts, totals = out
-            _check_range_out(ids, dist, counts, totals, nq, cap)
-        elif dev:
-            import torch
-            ids = torch.empty((nq, cap), dtype=torch.int64, device=queries.device)
-            dist = torch.empty((nq, cap), dtype=torch.float32, device=queries.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
-            totals = torch.empty((nq,), dtype=torch.int64, device=queries.device)
-        else:
-            ids = np.empty((nq, max(cap, 0)), np.int64)
-            dist = np.empty((nq, max(cap, 0)), np.float32)
-            counts = np.empty(nq, np.int32)
-            totals = np.empty(nq, np.int64)
+        ids, dist, counts, totals = _results("search_range", _range_spec(nq, cap), out, queries)
         p = self.params(flat_engine=engine)
         self._check(self.L.eps_index_search_range(self.h, _ptr(queries), nq, _ptr(radius), cap, C.byref(p), _ptr(ids), _ptr(dist), _ptr(counts),
                                                   _ptr(totals)))
@@ -462,13 +428,7 @@ class GpuIndex:
         rest -1 / +inf; the distances are a flat search's, bit for bit.  NumPy queries give NumPy results; device queries give device tensors
         and the call is asynchronous on the index's stream.  out=(ids, dist, counts): caller-provided buffers, all NumPy or all device."""
         k = int(k)
-        dev = _is_dev(queries)
-        if not dev:
-            queries = np.ascontiguousarray(queries, np.float32)
-            if queries.ndim == 1:
-                queries = queries[None, :]
-        nq = queries.shape[0]
-        assert queries.shape[1] == self.dim
+        queries, nq = _queries_2d(queries, self.dim)
         if _is_dev(ids):
             if str(ids.dtype) != "torch.int64" or ids.dim() != 1 or not ids.is_contiguous():
                 raise ValueError("search_among: device ids must be a contiguous 1-D int64 tensor, got %s %s" % (ids.dtype, tuple(ids.shape)))
@@ -480,22 +440,7 @@ class GpuIndex:
             offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_dev(offsets) else offsets), np.int64).reshape(-1)
             if offsets.size != nq + 1:
                 raise ValueError("search_among: offsets must hold nq + 1 = %d entries, got %d" % (nq + 1, offsets.size))
-        if out is not None:
-            out_ids, dist, counts = out
-            if len({_is_dev(a) for a in out}) != 1:
-                raise ValueError("search_among: out[ids], out[dist] and out[counts] must all be NumPy arrays or all be device tensors")
-            _check_out(out_ids, "ids", (nq, k), "int64")
-            _check_out(dist, "dist", (nq, k), "float32")
-            _check_out(counts, "counts", (nq,), "int32")
-        elif dev:
-            import torch
-            out_ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
-            dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=queries.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
-        else:
-            out_ids = np.empty((nq, max(k, 0)), np.int64)
-            dist = np.empty((nq, max(k, 0)), np.float32)
-            counts = np.empty(nq, np.int32)
+        out_ids, dist, counts = _results("search_among", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("counts", (nq,), "int32")), out, queries)
         self._keep["among"] = (queries, ids, offsets)   # (device results: the call is still running when this returns)
         self._check(self.L.eps_index_search_among(self.h, _ptr(queries), nq, _ptr(ids) if n_cand else None, _ptr(offsets), n_cand, k, _ptr(out_ids),
                                                   _ptr(dist), _ptr(counts)))
@@ -526,32 +471,9 @@ class GpuIndex:
         buffers, all NumPy or all device."""
         k = int(k)
         engine, flat_engine = GROUPS_ENGINES[engine], RANGE_ENGINES[flat_engine]
-        dev = _is_dev(queries)
-        if not dev:
-            queries = np.ascontiguousarray(queries, np.float32)
-            if queries.ndim == 1:
-                queries = queries[None, :]
-        nq = queries.shape[0]
-        assert queries.shape[1] == self.dim
-        if out is not None:
-            ids, dist, gkeys, counts = out
-            if len({_is_dev(a) for a in out}) != 1:
-                raise ValueError("search_groups: out[ids], out[dist], out[group_keys] and out[counts] must all be NumPy arrays or all be device tensors")
-            _check_out(ids, "ids", (nq, k), "int64")
-            _check_out(dist, "dist", (nq, k), "float32")
-            _check_out(gkeys, "group_keys", (nq, k), "int64")
-            _check_out(counts, "counts", (nq,), "int32")
-        elif dev:
-            import torch
-            ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
-            dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=queries.device)
-            gkeys = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
-        else:
-            ids = np.empty((nq, max(k, 0)), np.int64)
-            dist = np.empty((nq, max(k, 0)), np.float32)
-            gkeys = np.empty((nq, max(k, 0)), np.int64)
-            counts = np.empty(nq, np.int32)
+        queries, nq = _queries_2d(queries, self.dim)
+        ids, dist, gkeys, counts = _results("search_groups", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("group_keys", (nq, k), "int64"),
+                                                              ("counts", (nq,), "int32")), out, queries)
         p = self.params(flat_engine=flat_engine)
         self._keep["groups"] = (queries,)   # (device results: the call is still running when this returns)
         self._check(self.L.eps_index_search_groups(self.h, _ptr(queries), nq, k, C.byref(p), engine, int(page_rows), int(scratch_bytes),
@@ -568,39 +490,10 @@ class GpuIndex:
         counts): caller-provided buffers, all NumPy or all device."""
         k, m = int(k), int(m)
         engine, flat_engine = GROUPS_ENGINES[engine], RANGE_ENGINES[flat_engine]
-        dev = _is_dev(queries)
-        if not dev:
-            queries = np.ascontiguousarray(queries, np.float32)
-            if queries.ndim == 1:
-                queries = queries[None, :]
-        nq = queries.shape[0]
-        assert queries.shape[1] == self.dim
-        kk, mm = max(k, 0), max(m, 0)
-        if out is not None:
-            ids, dist, gkeys, rcounts, gsizes, counts = out
-            if len({_is_dev(a) for a in out}) != 1:
-                raise ValueError("search_group_rows: the out buffers must all be NumPy arrays or all be device tensors")
-            _check_out(ids, "ids", (nq, k, m), "int64")
-            _check_out(dist, "dist", (nq, k, m), "float32")
-            _check_out(gkeys, "group_keys", (nq, k), "int64")
-            _check_out(rcounts, "row_counts", (nq, k), "int32")
-            _check_out(gsizes, "group_sizes", (nq, k), "int64")
-            _check_out(counts, "counts", (nq,), "int32")
-        elif dev:
-            import torch
-            ids = torch.empty((nq, kk, mm), dtype=torch.int64, device=queries.device)
-            dist = torch.empty((nq, kk, mm), dtype=torch.float32, device=queries.device)
-            gkeys = torch.empty((nq, kk), dtype=torch.int64, device=queries.device)
-            rcounts = torch.empty((nq, kk), dtype=torch.int32, device=queries.device)
-            gsizes = torch.empty((nq, kk), dtype=torch.int64, device=queries.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
-        else:
-            ids = np.empty((nq, kk, mm), np.int64)
-            dist = np.empty((nq, kk, mm), np.float32)
-            gkeys = np.empty((nq, kk), np.int64)
-            rcounts = np.empty((nq, kk), np.int32)
-            gsizes = np.empty((nq, kk), np.int64)
-            counts = np.empty(nq, np.int32)
+        queries, nq = _queries_2d(queries, self.dim)
+        ids, dist, gkeys, rcounts, gsizes, counts = _results("search_group_rows", (
+            ("ids", (nq, k, m), "int64"), ("dist", (nq, k, m), "float32"), ("group_keys", (nq, k), "int64"), ("row_counts", (nq, k), "int32"),
+            ("group_sizes", (nq, k), "int64"), ("counts", (nq,), "int32")), out, queries)
         p = self.params(flat_engine=flat_engine)
         self._keep["group_rows"] = (queries,)   # (device results: the call is still running when this returns)
         self._check(self.L.eps_index_search_group_rows(self.h, _ptr(queries), nq, k, m, C.byref(p), engine, int(page_rows), int(scratch_bytes),
@@ -626,13 +519,47 @@ class GpuIndex:
         return {f: getattr(s, f) for f, _ in SearchStats._fields_}
 
 
-def _check_out(a, name, shape, dtype):
-    """a caller-provided result buffer (NumPy array or device tensor): dtype, shape and C-contiguity, or a ValueError instead of an out-of-bounds write"""
-    got_dtype = str(a.dtype).replace("torch.", "")
-    contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
-    if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
-        raise ValueError("search: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
-                         % (name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+def _queries_2d(queries, dim):
+    """(queries, nq) as the C ABI reads them: a device tensor as it is, anything else as C-contiguous float32 - one query per row, a single vector as one row"""
+    if not _is_dev(queries):
+        queries = np.ascontiguousarray(queries, np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+    assert queries.shape[1] == dim
+    return queries, queries.shape[0]
+
+
+def _check_bufs(who, bufs, one_kind=True, label="%s"):
+    """the one check of arrays the C ABI reads or writes through raw pointers.  bufs: (array, name, shape, dtype) - each C-contiguous, of that dtype
+    and shape, and (one_kind) all of them NumPy arrays or all device tensors; or a ValueError that names the call and the array (as label % name)
+    instead of an out-of-bounds access"""
+    if one_kind and len({_is_dev(a) for a, _, _, _ in bufs}) != 1:
+        names = [label % name for _, name, _, _ in bufs]
+        each = "both" if len(bufs) == 2 else "all"
+        raise ValueError("%s: %s and %s must %s be NumPy arrays or %s be device tensors" % (who, ", ".join(names[:-1]), names[-1], each, each))
+    for a, name, shape, dtype in bufs:
+        got_dtype = str(a.dtype).replace("torch.", "")
+        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
+        if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
+            raise ValueError("%s: %s must be a C-contiguous %s array of shape %s, got %s %s%s"
+                             % (who, label % name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+
+
+def _results(who, spec, out, like, one_kind=True):
+    """a call's result arrays from its spec - (name, shape, dtype) per result.  out given: the caller's buffers, checked against the spec (_check_bufs);
+    else new ones of the kind `like` is - NumPy arrays, or tensors on like's device"""
+    if out is None:
+        return tuple(_empty_like_kind(like, tuple(max(int(v), 0) for v in shape), dtype) for _, shape, dtype in spec)
+    out = tuple(out)
+    if len(out) != len(spec):
+        raise ValueError("%s: out must hold %d buffers (%s), got %d" % (who, len(spec), ", ".join(name for name, _, _ in spec), len(out)))
+    _check_bufs(who, tuple((a,) + tuple(s) for a, s in zip(out, spec)), one_kind, "out[%s]")
+    return out
+
+
+def _check_out(a, name, shape, dtype, who="search"):
+    """one caller-provided result buffer of the call `who`"""
+    _check_bufs(who, ((a, name, shape, dtype),), one_kind=False, label="out[%s]")
 
 
 RANGE_ENGINES = {"auto": FLAT_AUTO, "stream": FLAT_STREAM, "mfma": FLAT_MFMA, "mfma_i8": FLAT_MFMA_I8,
@@ -643,31 +570,18 @@ GROUPS_AUTO, GROUPS_PAGES, GROUPS_SCAN = 0, 1, 2
 GROUPS_ENGINES = {"auto": GROUPS_AUTO, "pages": GROUPS_PAGES, "scan": GROUPS_SCAN, GROUPS_AUTO: GROUPS_AUTO, GROUPS_PAGES: GROUPS_PAGES, GROUPS_SCAN: GROUPS_SCAN}
 
 
+def _range_spec(nq, cap):
+    return (("ids", (nq, cap), "int64"), ("dist", (nq, cap), "float32"), ("counts", (nq,), "int32"), ("totals", (nq,), "int64"))
+
+
 def _check_range_out(ids, dist, counts, totals, nq, cap):
-    """search_range's caller-provided buffers: ids int64 [nq, cap], dist float32 [nq, cap], counts int32 [nq], totals int64 [nq], C-contiguous, all
-    NumPy arrays or all device tensors - or a ValueError instead of an out-of-bounds write"""
-    bufs = ((ids, "ids", (nq, cap), "int64"), (dist, "dist", (nq, cap), "float32"), (counts, "counts", (nq,), "int32"), (totals, "totals", (nq,), "int64"))
-    if len({_is_dev(a) for a, _, _, _ in bufs}) != 1:
-        raise ValueError("search_range: out[ids], out[dist], out[counts] and out[totals] must all be NumPy arrays or all be device tensors")
-    for a, name, shape, dtype in bufs:
-        got_dtype = str(a.dtype).replace("torch.", "")
-        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
-        if got_dtype != dtype or tuple(a.shape) != shape or not contiguous:
-            raise ValueError("search_range: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
-                             % (name, dtype, shape, got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+    """search_range's caller-provided buffers (and the range merges'): ids int64 [nq, cap], dist float32 [nq, cap], counts int32 [nq], totals int64 [nq]"""
+    _results("search_range", _range_spec(nq, cap), (ids, dist, counts, totals), None)
 
 
 def _check_select_out(ids, counts, limit):
-    """select's caller-provided buffers: ids int64 [limit] and counts int64 [2], C-contiguous, both NumPy arrays or both device tensors - or a
-    ValueError instead of an out-of-bounds write"""
-    if _is_dev(ids) != _is_dev(counts):
-        raise ValueError("select: out[ids] and out[counts] must both be NumPy arrays or both be device tensors")
-    for a, name, shape in ((ids, "ids", (limit,)), (counts, "counts", (2,))):
-        got_dtype = str(a.dtype).replace("torch.", "")
-        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
-        if got_dtype != "int64" or tuple(a.shape) != shape or not contiguous:
-            raise ValueError("select: out[%s] must be a C-contiguous int64 array of shape %s, got %s %s%s"
-                             % (name, shape, got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
+    """select's caller-provided buffers (and merge_select's): ids int64 [limit] and counts int64 [2]"""
+    _results("select", (("ids", (limit,), "int64"), ("counts", (2,), "int64")), (ids, counts), None)
 
 
 def traversal_gather_bytes(stats, dim, avg_degree, seed_evals=0):
@@ -837,18 +751,6 @@ def _empty_like_kind(like, shape, dtype):
     return np.empty(shape, dtype)
 
 
-def _check_lists(what, bufs):
-    """bufs: (array, name, shape, dtype) - all NumPy or all device, C-contiguous, of that dtype and shape; or a ValueError before the C ABI reads them"""
-    if len({_is_dev(a) for a, _, _, _ in bufs}) != 1:
-        raise ValueError("%s: %s must all be NumPy arrays or all be device tensors" % (what, ", ".join(name for _, name, _, _ in bufs)))
-    for a, name, shape, dtype in bufs:
-        got_dtype = str(a.dtype).replace("torch.", "")
-        contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
-        if got_dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
-            raise ValueError("%s: %s must be a C-contiguous %s array of shape %s, got %s %s%s"
-                             % (what, name, dtype, tuple(shape), got_dtype, tuple(a.shape), "" if contiguous else " (not contiguous)"))
-
-
 def _merge_refusal(shards, cap=1, nq=0, length=0, skip=0, limit=0):
     """why the library refused a merge (it has no handle to leave a message in)"""
     why = []
@@ -876,11 +778,10 @@ def merge_range(ids, dist, counts, totals, out=None, device=0, stream=None):
     if len(ids.shape) != 3:
         raise ValueError("merge_range: ids must have shape [shards, nq, cap], got %s" % (tuple(ids.shape),))
     shards, nq, cap = (int(v) for v in ids.shape)
-    _check_lists("merge_range", ((ids, "ids", (shards, nq, cap), "int64"), (dist, "dist", (shards, nq, cap), "float32"),
-                                 (counts, "counts", (shards, nq), "int32"), (totals, "totals", (shards, nq), "int64")))
+    _check_bufs("merge_range", ((ids, "ids", (shards, nq, cap), "int64"), (dist, "dist", (shards, nq, cap), "float32"),
+                                (counts, "counts", (shards, nq), "int32"), (totals, "totals", (shards, nq), "int64")))
     if out is None:
-        out = (_empty_like_kind(ids, (nq, cap), "int64"), _empty_like_kind(ids, (nq, cap), "float32"), _empty_like_kind(ids, (nq,), "int32"),
-               _empty_like_kind(ids, (nq,), "int64"))
+        out = _results("merge_range", _range_spec(nq, cap), None, ids)
     _check_range_out(*out, nq, cap)
     if _is_dev(out[0]) != _is_dev(ids):
         raise ValueError("merge_range: lists and out= must all be NumPy arrays or all be device tensors")
@@ -901,8 +802,7 @@ def merge_range_packed(gathered, shard_stride_bytes, shards, nq, cap, out=None, 
         raise ValueError("merge_range_packed: gathered holds %d bytes, %d shards of %d bytes are needed"
                          % (gathered.numel() * gathered.element_size(), shards, shard_stride_bytes))
     if out is None:
-        out = (_empty_like_kind(gathered, (nq, max(cap, 0)), "int64"), _empty_like_kind(gathered, (nq, max(cap, 0)), "float32"),
-               _empty_like_kind(gathered, (nq,), "int32"), _empty_like_kind(gathered, (nq,), "int64"))
+        out = _results("merge_range_packed", _range_spec(nq, cap), None, gathered)
     _check_range_out(*out, nq, cap)
     rc = L.eps_merge_range_packed(_ptr(gathered), int(shard_stride_bytes), shards, nq, cap, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
                                   device, C.c_void_p(stream) if stream else None)
@@ -923,7 +823,7 @@ def merge_select(ids, counts, totals, skip=0, limit=None, out=None, device=0, st
     shards, length = (int(v) for v in ids.shape)
     skip = int(skip)
     limit = max(length - skip, 0) if limit is None else int(limit)
-    _check_lists("merge_select", ((ids, "ids", (shards, length), "int64"), (counts, "counts", (shards,), "int64"), (totals, "totals", (shards,), "int64")))
+    _check_bufs("merge_select", ((ids, "ids", (shards, length), "int64"), (counts, "counts", (shards,), "int64"), (totals, "totals", (shards,), "int64")))
     if out is None:
         out = (_empty_like_kind(ids, (max(limit, 0),), "int64"), _empty_like_kind(ids, (2,), "int64"))
     out_ids, out_counts = out

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib as lib
 from ._lib import EpsillaError, SearchStats
-from .index import METRICS, _is_dev, _ptr
+from .index import METRICS, _is_dev, _ptr, _results
 
 MAX_K = 1024
 
@@ -46,13 +46,6 @@ def _csr(offsets, indices, values, who):
     if not _is_dev(offsets) and int(offsets[-1]) != _size(indices):
         raise ValueError("%s: offsets[-1] = %d, but indices and values hold %d entries" % (who, int(offsets[-1]), _size(indices)))
     return offsets, indices, values, _size(offsets) - 1
-
-
-def _check_out(a, name, shape, dtype):
-    contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else bool(a.flags["C_CONTIGUOUS"])
-    if _dtype(a) != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
-        raise ValueError("search: out[%s] must be a C-contiguous %s array of shape %s, got %s %s%s"
-                         % (name, dtype, tuple(shape), _dtype(a), tuple(a.shape), "" if contiguous else " (not contiguous)"))
 
 
 def queries_from_dicts(queries):
@@ -135,21 +128,7 @@ class GpuSparseIndex:
         if _is_dev(q_idx) != _is_dev(q_val):
             raise ValueError("search: the queries' indices and values must both be NumPy arrays or both be device tensors")
         q_off, q_idx, q_val, nq = _csr(q_off, q_idx, q_val, "search")
-        dev = _is_dev(q_idx)
-        if out is not None:
-            ids, dist, counts = out
-            if len({_is_dev(a) for a in out}) != 1:
-                raise ValueError("search: out[ids], out[dist] and out[counts] must all be NumPy arrays or all be device tensors")
-            _check_out(ids, "ids", (nq, k), "int64")
-            _check_out(dist, "dist", (nq, k), "float32")
-            _check_out(counts, "counts", (nq,), "int32")
-        elif dev:
-            import torch
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q_idx.device)
-            dist = torch.empty((nq, k), dtype=torch.float32, device=q_idx.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=q_idx.device)
-        else:
-            ids, dist, counts = np.empty((nq, k), np.int64), np.empty((nq, k), np.float32), np.empty(nq, np.int32)
+        ids, dist, counts = _results("search", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("counts", (nq,), "int32")), out, q_idx)
         self._keep["queries"] = (q_off, q_idx, q_val)   # (device results: the call is still running when this returns)
         nnz = _size(q_idx)
         self._check(self.L.eps_sparse_index_search(self.h, _ptr(q_off), _ptr(q_idx) if nnz else None, _ptr(q_val) if nnz else None, nq, k, _ptr(ids),
