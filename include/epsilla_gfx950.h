@@ -32,6 +32,8 @@
  *                                   grouping of a finished answer (FacetExecutor, db/execution/aggregation.hpp) - it has no grouped search
  *   eps_index_search_group_rows     (new) ... and of each of those groups its m closest rows and the number of its visible rows: the
  *                                   `group_size` of a grouped search; the reference has no relative
+ *   eps_index_search_multi          (new) the k closest groups for a query that is itself several vectors, by the sum over them of the distance
+ *                                   to the group's closest row - the late-interaction score of a chunk table; the reference has no relative
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
  *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
@@ -536,6 +538,41 @@ int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_
 int32_t eps_index_search_group_rows(eps_index* h, const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine,
                                     int32_t page_rows, int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out,
                                     int32_t* row_counts_out, int64_t* group_sizes_out, int32_t* counts_out);
+/* Multi-vector queries: the k closest groups by summed closest rows - the late-interaction score (the negated MaxSim under DOT_PRODUCT, a one-sided
+ * Chamfer distance under L2) of a query that is a bag of vectors against documents that are groups of rows.  Before, a caller ran
+ * eps_index_search with k = n per vector and reduced on the host: eps_index_search_groups lists only k <= 1024 groups per vector.
+ * The rule.  Query j is the bag vectors[q_offsets[j] .. q_offsets[j + 1]) of t_j vectors, 0 <= t_j <= 1024.  For a vector u of the bag: V_u = the
+ * visible rows exactly as eps_index_search_groups defines them for a query u (not deleted, passing the int-column test and the installed program,
+ * `@distance` reading the exact distance of (row, u)); the distance of (row, u) is, bit for bit, what eps_index_search in EPS_MODE_FLAT returns;
+ * b(u, g) = the smallest (distance, row) key over V_u n g - ties to the smaller row, NaN after +inf: the representative eps_index_search_groups
+ * would return for u if g made its list; d(u, g) = its distance.  A group g QUALIFIES for bag j iff V_u n g is non-empty for every u of the bag; a
+ * bag of t_j = 0 has no qualifying group.  score(j, g): s = +0.0f, then s = s + d(u, g) in fp32 for u in bag order, one add after the other -
+ * nothing is reassociated, a NaN or an infinite term propagates as IEEE 754 says.  The qualifying groups are ordered by (score, group key): every
+ * NaN score takes the one place after +inf, ties go to the smaller int64 key.  The answer is the k smallest; counts_out[j] = min(k, qualifying).
+ * Candidates.  cand_keys == NULL: every group of eps_index_set_groups is considered.  Else only the groups whose keys the caller names: one list
+ * cand_keys[0 .. n_cand) for every bag (cand_offsets == NULL), or bag j's list cand_keys[cand_offsets[j] .. cand_offsets[j + 1]) - cand_offsets a
+ * host int64[nq + 1] checked as eps_index_search_among checks its offsets.  A key that names no group is ignored, a key named several times counts
+ * once.  Both forms return the same bits: the second stage of a pipeline whose first stage found candidate documents by any means.
+ * vectors: host or device float[T][dim], T = q_offsets[nq] < 2^31 (COSINE: normalised already); q_offsets: host int64[nq + 1], [0] = 0,
+ * non-decreasing; cand_keys: host (copied) or device (used in place) int64[n_cand], 0 <= n_cand < 2^31.  group_keys_out, score_out [nq][k];
+ * counts_out [nq], may be NULL; match_ids_out / match_dist_out, both NULL or neither, k * T elements: the entry of bag j, slot s, vector u lies at
+ * k * q_offsets[j] + s * t_j + u and holds the row of b(u, g_s) (through eps_index_set_id_map) and d(u, g_s) - the chunk that matched each query
+ * vector.  Unused slots: key 0 / +inf / -1 / +inf.  The outputs are all host or all device.  Host arrays are read before the call returns, device
+ * arrays at the call's place in the index's stream; with device outputs the call does not synchronise the host (the first candidate-form call
+ * after eps_index_set_groups builds the rows by group, as eps_index_search_group_rows does: a set-up step with one sync).
+ * 1 <= k <= 1024, t_j <= 1024, well-formed offsets, else EPS_USER_ERROR; nq = 0: EPS_OK.  No groups set, stale labels, stale filters, a null required
+ * buffer, outputs of mixed kinds: the errors of eps_index_search_groups.  A sharded handle: EPS_DB_UNSUPPORTED_ERROR.
+ * A bag is never cut: the vectors of as many whole bags as fit share one table of 8-byte keys - t_j x G of them per bag in the whole-table form,
+ * t_j x its candidates in the candidate form.  scratch_bytes = 0: max(256 MiB, the largest bag's table); a positive value is a cap, and a bag
+ * whose own table exceeds it is refused with EPS_DB_UNSUPPORTED_ERROR before any launch, the message naming the bytes needed.
+ * Whole-table form (csrc/multi.hip): eps_index_search_groups' scan with the bag vectors as its queries, then a sum and top-k over the table's
+ * columns; n * dim * 4 + n * 4 bytes of traffic per 4 vectors plus 8 * t_j * G per bag.  Candidate form: the rows of the named groups, through the
+ * rows by group, once per 4 vectors per bag that names them.  eps_index_last_stats reports the call like a search: dist_evals = the (row, vector)
+ * pairs given a distance, main_kernel_bits = 32, main_kernel_ms = the scan or the gather.  eps_index_groups_info and everything else a later call
+ * can observe are unchanged. */
+int32_t eps_index_search_multi(eps_index* h, const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys,
+                               const int64_t* cand_offsets, int64_t n_cand, int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out,
+                               int32_t* counts_out, int64_t* match_ids_out, float* match_dist_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

@@ -277,6 +277,11 @@ int32_t eps_index_search_group_rows(eps_index* h, const float* q, int64_t nq, in
                                     int32_t* counts) {
   GUARD(h, IX(h)->search_group_rows(q, nq, k, m, p, engine, page_rows, scratch_bytes, ids, dist, group_keys, row_counts, group_sizes, counts));
 }
+int32_t eps_index_search_multi(eps_index* h, const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys, const int64_t* cand_offsets,
+                               int64_t n_cand, int32_t k, int64_t scratch_bytes, int64_t* group_keys, float* score, int32_t* counts, int64_t* match_ids,
+                               float* match_dist) {
+  GUARD(h, IX(h)->search_multi(vectors, q_offsets, nq, cand_keys, cand_offsets, n_cand, k, scratch_bytes, group_keys, score, counts, match_ids, match_dist));
+}
 int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) {
   GUARD(h, IX(h)->groups_info(n_groups, largest_group, last_engines, last_scan_queries));
 }

@@ -125,6 +125,9 @@ class IndexBase {
   virtual int32_t search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine, int32_t page_rows,
                                     int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* row_counts_out,
                                     int64_t* group_sizes_out, int32_t* counts_out) = 0;
+  virtual int32_t search_multi(const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys, const int64_t* cand_offsets,
+                               int64_t n_cand, int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out, int32_t* counts_out,
+                               int64_t* match_ids_out, float* match_dist_out) = 0;
   virtual int64_t row_count() const = 0;
   virtual int32_t last_stats(eps_search_stats* out) = 0;
   virtual int kernel_times(double* ms_out, int cap) = 0;
@@ -195,6 +198,11 @@ class Index : public IndexBase {
   int32_t search_group_rows(const float* queries, int64_t nq, int32_t k, int32_t m, const eps_search_params* p, int32_t engine, int32_t page_rows,
                             int64_t scratch_bytes, int64_t* ids_out, float* dist_out, int64_t* group_keys_out, int32_t* row_counts_out, int64_t* group_sizes_out,
                             int32_t* counts_out) override;
+  // the k closest groups per BAG of vectors, by the sum over the bag of each vector's distance to the group's closest visible row; over every
+  // group or over the groups the caller names (eps_index_search_multi; multi.hip, plan: multi_host.hpp)
+  int32_t search_multi(const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys, const int64_t* cand_offsets, int64_t n_cand,
+                       int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out, int32_t* counts_out, int64_t* match_ids_out,
+                       float* match_dist_out) override;
 
   int64_t row_count() const override { return n_rows_; }
 
@@ -282,6 +290,10 @@ class Index : public IndexBase {
   // the labels; [pair counter | sizes | work-item prefix] of a pass; the pairs' merged lists
   DevBuf grp_offsets_, grp_rowlist_, grp_work_, grp_rows_run_;
   bool grp_by_group_ = false;
+  // search_multi(): [pair counter | bag offsets | table elements and pairs in front of every bag | candidate offsets | a host list's keys]; the
+  // candidates' labels; the gather's work-item prefix.  Its tables, partial and merged lists are the scan's (grp_table_, partial_buf_, grp_run_)
+  DevBuf multi_in_, multi_label_, multi_prefix_;
+  int32_t ensure_rows_by_group(const char* who);
   int32_t groups_ready(const char* who);
   void forget_rows_by_group();
   int32_t groups_representatives(const char* who, const float* dq, int64_t nq, int32_t k, const eps_search_params& p, int32_t engine, int32_t page_rows,

@@ -1,4 +1,4 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, the steps they share (their results: result_block.hpp), and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, search_multi, the steps they share (their results: result_block.hpp), and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
@@ -753,6 +753,24 @@ void Index::forget_rows_by_group() {
   grp_by_group_ = false;
 }
 
+// The rows by group (offsets[G + 1], rows[n]; group_rows.hip) for the calls that walk a group's rows: built at the first such call after a
+// set_groups - histogram, scan, scatter, one stream sync - and kept until the labels go
+int32_t Index::ensure_rows_by_group(const char* who) {
+  const int64_t n = n_rows_, G = grp_n_groups_;
+  if (grp_by_group_ || n <= 0) return EPS_OK;
+  DevBuf cursor;
+  if (!grp_offsets_.reserve((size_t)(G + 1) * sizeof(int64_t)) || !grp_rowlist_.reserve((size_t)n * sizeof(int32_t)) || !cursor.reserve((size_t)G * sizeof(u32))) {
+    forget_rows_by_group();
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of device memory (the rows by group)");
+  }
+  HIP_TRY(hipMemsetAsync(cursor.p, 0, (size_t)G * sizeof(u32), stream_));
+  launch_group_rows_build(grp_label_.as<int32_t>(), n, G, cursor.as<u32>(), grp_offsets_.as<int64_t>(), grp_rowlist_.as<int32_t>(), stream_);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(stream_));   // (the cursors end here)
+  grp_by_group_ = true;
+  return EPS_OK;
+}
+
 // The k closest groups per query and the m closest visible rows of each (group_rows.hip, plan: group_rows_host.hpp).  Phase 1 is search_groups'
 // (groups_representatives); phase 2 - work list, gather, merge, result conversion - reads what phase 1 left on the device and has no host sync of
 // its own, so with EPS_GROUPS_SCAN and device results the call stays asynchronous.  The rows by group (offsets[G + 1], rows[n]) are built on the
@@ -782,19 +800,9 @@ int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, in
   rc = check_filters_cover_table("search_group_rows");
   if (rc != EPS_OK) return rc;
 
-  const int64_t n = n_rows_, G = grp_n_groups_;
-  if (!grp_by_group_ && n > 0) {   // the set-up step: histogram, scan, scatter
-    DevBuf cursor;
-    if (!grp_offsets_.reserve((size_t)(G + 1) * sizeof(int64_t)) || !grp_rowlist_.reserve((size_t)n * sizeof(int32_t)) || !cursor.reserve((size_t)G * sizeof(u32))) {
-      forget_rows_by_group();
-      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_group_rows: out of device memory (the rows by group)");
-    }
-    HIP_TRY(hipMemsetAsync(cursor.p, 0, (size_t)G * sizeof(u32), stream_));
-    launch_group_rows_build(grp_label_.as<int32_t>(), n, G, cursor.as<u32>(), grp_offsets_.as<int64_t>(), grp_rowlist_.as<int32_t>(), stream_);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream_));   // (the cursors end here)
-    grp_by_group_ = true;
-  }
+  const int64_t n = n_rows_;
+  rc = ensure_rows_by_group("search_group_rows");
+  if (rc != EPS_OK) return rc;
   begin_timed_call();
   prefilter_call_ = false;   // (@distance reads the row's exact distance)
 
@@ -857,6 +865,185 @@ int32_t Index::search_group_rows(const float* queries, int64_t nq, int32_t k, in
   launch_groups_keys(res, nq, k, grp_label_.as<int32_t>(), grp_keys_.as<int64_t>(), rb.dev(r_gk), stream_);
   if (n > 0) set_main_kernel(1, n, nq, 32);
   rc = publish_device_evals(d_evals);   // (the second phase's pairs: last_stats adds them)
+  if (rc != EPS_OK) return rc;
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(rb);
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ search_multi
+// The k closest groups per bag of vectors by the sum of each vector's distance to the group's closest visible row (multi.hip, plan: multi_host.hpp).
+// cand_keys null: the whole-table form - search_groups' scan with the vectors of whole bags as its pseudo-queries, then sums, top-k and the answer
+// read from the table.  Else the candidate form: labels of the named keys, work list, gather into a table per (bag, candidate) pair, then the same
+// sums, top-k and answer.  No host sync of its own in either form.  Reports like a search; changes nothing a later call can observe.
+int32_t Index::search_multi(const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys, const int64_t* cand_offsets, int64_t n_cand,
+                            int32_t k, int64_t scratch_bytes, int64_t* group_keys, float* score, int32_t* counts, int64_t* match_ids, float* match_dist) {
+  const char* why;
+  if (multi_args_check(nq, k, n_cand, scratch_bytes, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_multi: ") + why);
+  if (nq == 0) return EPS_OK;
+  HIP_TRY(hipSetDevice(device_));
+  if (!q_offsets) return fail(EPS_USER_ERROR, "search_multi: null buffer");
+  if (is_device_ptr(q_offsets)) return fail(EPS_USER_ERROR, "search_multi: q_offsets must be a host array");
+  int64_t T = 0, t_max = 0, longest = 0;
+  if (multi_bags_check(q_offsets, nq, &T, &t_max, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_multi: ") + why);
+  const bool cand = cand_keys != nullptr;
+  if (!cand && (cand_offsets || n_cand > 0)) return fail(EPS_USER_ERROR, "search_multi: null buffer");   // (a list without its keys)
+  if (cand_offsets && is_device_ptr(cand_offsets)) return fail(EPS_USER_ERROR, "search_multi: cand_offsets must be a host array");
+  if (cand && among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_multi: ") + why);
+  int32_t rc = groups_ready("search_multi");
+  if (rc != EPS_OK) return rc;
+  if ((T > 0 && !vectors) || !group_keys || !score || (match_ids == nullptr) != (match_dist == nullptr)) return fail(EPS_USER_ERROR, "search_multi: null buffer");
+  ResultBlock rb;
+  const auto r_gk = rb.add(group_keys, (size_t)nq * k);
+  const auto r_mid = rb.add(match_ids, match_ids ? (size_t)T * k : 0);
+  const auto r_score = rb.add(score, (size_t)nq * k);
+  const auto r_md = rb.add(match_dist, match_dist ? (size_t)T * k : 0);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search_multi: the output buffers must all be host or all be device pointers");
+  const bool out_dev = rb.device();
+  rc = check_filters_cover_table("search_multi");
+  if (rc != EPS_OK) return rc;
+
+  // ---- the plan, and the refusal of a bag that cannot be served whole - before any launch
+  const int64_t n = n_rows_, G = grp_n_groups_;
+  std::vector<int64_t> h_in((size_t)(nq + 1) * (cand ? (cand_offsets ? 4 : 3) : 1));   // [q_off | elements in front | pairs in front | cand_off]
+  int64_t* const h_qoff = h_in.data();
+  int64_t* const h_elems = cand ? h_qoff + (nq + 1) : h_qoff;
+  int64_t* const h_pairs = cand ? h_elems + (nq + 1) : nullptr;
+  std::memcpy(h_qoff, q_offsets, (size_t)(nq + 1) * sizeof(int64_t));
+  int64_t largest_bytes = t_max * G * 8;
+  if (cand) {
+    if (cand_offsets) std::memcpy(h_pairs + (nq + 1), cand_offsets, (size_t)(nq + 1) * sizeof(int64_t));
+    h_elems[0] = h_pairs[0] = 0;
+    largest_bytes = 0;
+    for (int64_t j = 0; j < nq; ++j) {   // (T, n_cand < 2^31: the totals stay below 2^62)
+      const int64_t nc = cand_offsets ? cand_offsets[j + 1] - cand_offsets[j] : n_cand, t = q_offsets[j + 1] - q_offsets[j];
+      h_pairs[j + 1] = h_pairs[j] + nc;
+      h_elems[j + 1] = h_elems[j] + nc * t;
+      largest_bytes = std::max(largest_bytes, nc * t * 8);
+    }
+  }
+  int64_t cap_bytes = 0;
+  if (!multi_scratch_cap(scratch_bytes, largest_bytes, &cap_bytes))
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "search_multi: a bag's own table needs " + std::to_string(largest_bytes) + " bytes, scratch_bytes allows " +
+                                              std::to_string(scratch_bytes) + " (a bag is never cut)");
+  const MultiTopkPlan plan = multi_topk_plan(cand ? longest : G, k);
+  const int64_t cap_a = cand ? cap_bytes / 8 : multi_table_vectors(cap_bytes, G);
+  if (cand) {
+    rc = ensure_rows_by_group("search_multi");
+    if (rc != EPS_OK) return rc;
+  }
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the row's exact distance)
+
+  const float* dq = vectors;
+  if (T > 0) {
+    rc = stage_queries("search_multi", vectors, T, &dq, !out_dev);
+    if (rc != EPS_OK) return rc;
+  }
+
+  // ---- scratch: [pair counter | the offsets above | a host list's keys], the candidates' labels; per pass: table, work list, partial and merged lists
+  int64_t pass_elems = 0, pass_pairs = 0, pass_bags = 0;
+  for (int64_t j0 = 0; j0 < nq;) {
+    const int64_t j1 = multi_slice_end(h_elems, cap_a, h_pairs, MULTI_MAX_PAIRS, nq, j0, plan.bags);
+    pass_elems = std::max(pass_elems, (h_elems[j1] - h_elems[j0]) * (cand ? 1 : G));
+    if (cand) pass_pairs = std::max(pass_pairs, h_pairs[j1] - h_pairs[j0]);
+    pass_bags = std::max(pass_bags, j1 - j0);
+    j0 = j1;
+  }
+  const bool keys_dev = cand && n_cand > 0 && is_device_ptr(cand_keys);
+  const size_t in_bytes = h_in.size() * sizeof(int64_t), list_bytes = (cand && !keys_dev) ? (size_t)n_cand * sizeof(int64_t) : 0;
+  if (!multi_in_.reserve(8 + in_bytes + list_bytes) || !grp_table_.reserve((size_t)pass_elems * sizeof(u64)) ||
+      !partial_buf_.reserve((size_t)pass_bags * plan.W * k * sizeof(u64)) || !grp_run_.reserve((size_t)pass_bags * k * sizeof(u64)) ||
+      (cand && (!multi_label_.reserve((size_t)n_cand * sizeof(int32_t)) || !multi_prefix_.reserve((size_t)(pass_pairs + 1) * sizeof(unsigned long long)))) ||
+      !rb.place(out_block_))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_multi: out of device memory (scratch)");
+  if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_multi: out of page-locked host memory");
+  unsigned long long* d_evals = multi_in_.as<unsigned long long>();
+  int64_t* const d_in = multi_in_.as<int64_t>() + 1;
+  rc = clear_device_evals(d_evals);
+  if (rc != EPS_OK) return rc;
+  rc = copy_host_in(d_in, h_in.data(), in_bytes, !out_dev);
+  if (rc != EPS_OK) return rc;
+  const int64_t* d_keys = cand_keys;
+  if (cand && !keys_dev && n_cand > 0) {
+    d_keys = reinterpret_cast<const int64_t*>(multi_in_.as<char>() + 8 + in_bytes);
+    rc = copy_host_in(const_cast<int64_t*>(d_keys), cand_keys, list_bytes, !out_dev);
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+  if (cand) launch_multi_labels(d_keys, n_cand, grp_keys_.as<int64_t>(), G, multi_label_.as<int32_t>(), stream_);
+
+  MultiArgs a;
+  a.rows = d_rows_;
+  a.dim = (int)dim_;
+  a.metric = metric_;
+  a.f = filter_spec();
+  a.vectors = dq;
+  a.q_off = d_in;
+  a.k = k;
+  a.G = G;
+  a.table = grp_table_.as<u64>();
+  a.base_off = cand ? d_in + (nq + 1) : d_in;
+  a.plan = plan;
+  a.partial = partial_buf_.as<u64>();
+  a.run_keys = grp_run_.as<u64>();
+  a.cand_label = cand ? multi_label_.as<int32_t>() : nullptr;
+  if (cand && n_cand == 0) a.cand_label = reinterpret_cast<const int32_t*>(d_in);   // (never read: no bag has a candidate; non-null marks the form)
+  a.cand_off = cand_offsets ? d_in + 3 * (nq + 1) : nullptr;
+  a.n_cand = n_cand;
+  a.offsets = grp_offsets_.as<int64_t>();
+  a.group_rows = grp_rowlist_.as<int32_t>();
+  a.prefix = multi_prefix_.as<unsigned long long>();
+  a.evals = d_evals;
+  int64_t launches = 0, vectors_scanned = 0;
+  for (int64_t j0 = 0; j0 < nq;) {
+    const int64_t j1 = multi_slice_end(h_elems, cap_a, h_pairs, MULTI_MAX_PAIRS, nq, j0, plan.bags);
+    a.j0 = j0;
+    a.bags = j1 - j0;
+    const int64_t elems = (h_elems[j1] - h_elems[j0]) * (cand ? 1 : G);
+    a.pairs = cand ? h_pairs[j1] - h_pairs[j0] : 0;
+    if (elems > 0 && n > 0) {
+      launch_fill_u64(a.table, elems, KEY_EMPTY, stream_);
+      HIP_TRY(hipEventRecord(evk0_, stream_));
+      if (cand) {
+        a.waves = std::min<int64_t>(MULTI_MAX_WAVES, a.pairs * multi_pair_items(grp_largest_, t_max));   // (pairs < 2^31, items < 2^31)
+        launch_multi_gather(a, stream_);
+      } else {
+        const int64_t m = h_qoff[j1] - h_qoff[j0];
+        GroupsScanArgs g;
+        g.rows = d_rows_;
+        g.n = n;
+        g.dim = (int)dim_;
+        g.metric = metric_;
+        g.queries = dq + h_qoff[j0] * dim_;
+        g.m = m;
+        g.qsel = nullptr;
+        g.f = a.f;
+        g.label = grp_label_.as<int32_t>();
+        g.best = a.table;
+        g.G = G;
+        g.W = flat_scan_waves(n, m, (int)dim_);
+        launch_groups_min_scan(g, stream_);
+        vectors_scanned += m;
+      }
+      HIP_TRY(hipEventRecord(evk1_, stream_));
+      launches = 1;
+    }
+    launch_multi_sum_topk(a, stream_);
+    launch_among_merge(a.partial, plan.W, k, a.bags, a.run_keys, stream_);
+    launch_multi_finalize(a, grp_keys_.as<int64_t>(), id_base_, id_stride_, rb.dev(r_gk), rb.dev(r_score), rb.dev(r_cnt),
+                          match_ids ? rb.dev(r_mid) : nullptr, match_ids ? rb.dev(r_md) : nullptr, stream_);   // (no matches asked for: their parts are empty)
+    j0 = j1;
+  }
+  set_main_kernel(launches, cand ? n_cand : n, cand ? nq : vectors_scanned, 32);
+  stats_.dist_evals += vectors_scanned * n;
+  rc = publish_device_evals(d_evals);   // (the gather's pairs: last_stats adds them)
   if (rc != EPS_OK) return rc;
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {

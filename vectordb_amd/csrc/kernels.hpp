@@ -9,6 +9,7 @@
 #include "group_rows_host.hpp"
 #include "groups_host.hpp"
 #include "merge_host.hpp"
+#include "multi_host.hpp"
 #include "sparse_host.hpp"
 #include "sparse_inv_host.hpp"
 
@@ -275,6 +276,45 @@ void launch_group_rows_merge(const GroupRowsArgs& a, hipStream_t s);
 // ids [pairs][m] through the id map, dist [pairs][m], row_counts [pairs], group_sizes [pairs] (may be null), counts [pairs / k] (may be null)
 void launch_group_rows_finalize(const GroupRowsArgs& a, int64_t id_base, int64_t id_stride, int64_t* ids, float* dist, int32_t* row_counts,
                                 int64_t* group_sizes, int32_t* counts, hipStream_t s);
+
+// ---------------------------------------------------------------- multi-vector search (eps_index_search_multi; multi.hip, plan: multi_host.hpp)
+struct MultiArgs {             // one pass: whole bags [j0, j0 + bags) of the call's nq
+  const float* rows;
+  int dim, metric;
+  FilterSpec f;
+  const float* vectors;        // [T][dim] the vectors of every bag of the call
+  const int64_t* q_off;        // [nq + 1] bag j = vectors[q_off[j] .. q_off[j + 1])
+  int64_t j0, bags;
+  int k;
+  int64_t G;                   // labels
+  // the pass's table of minimum keys, KEY_EMPTY before the launches.  Whole-table form: best[vector of the pass][G].  Candidate form:
+  // pair_best[(bag, candidate) pair][t of the bag], bag j's pairs from element base_off[j] - base_off[j0]
+  u64* table;
+  const int64_t* base_off;     // [nq + 1] whole-table form: q_off; candidate form: table elements in front of bag j's pairs
+  MultiTopkPlan plan;          // how the table's columns (labels; a bag's candidates) are cut among the read-back's wavefronts
+  u64* partial;                // [bags][plan.W][k]
+  u64* run_keys;               // [bags][k] make_key(score, label), sorted, unique
+  // candidate form only (cand_label == null: the whole-table form)
+  const int32_t* cand_label;   // [n_cand] the label a candidate key names, -1: none
+  const int64_t* cand_off;     // [nq + 1] bag j's candidates = [cand_off[j], cand_off[j + 1]); null: [0, n_cand) for every bag
+  int64_t n_cand;
+  int64_t pairs;               // (bag, candidate) pairs of the pass
+  const int64_t* offsets;      // [G + 1] the rows by group (group_rows.hip)
+  const int32_t* group_rows;   // [n]
+  unsigned long long* prefix;  // [pairs + 1] work items of the pairs in front; [pairs]: all of them (written by the launch, never read by the host)
+  int64_t waves;               // wavefronts of the gather's grid
+  unsigned long long* evals;   // (row, vector) pairs given a distance, added to
+};
+// cand_label[i] = the label whose key is cand_keys[i], -1 where no group has that key
+void launch_multi_labels(const int64_t* cand_keys, int64_t n_cand, const int64_t* key_of_label, int64_t G, int32_t* cand_label, hipStream_t s);
+// candidate form: the work list, then the gather over it into a.table
+void launch_multi_gather(const MultiArgs& a, hipStream_t s);
+// the table's columns into a.partial: per bag and wavefront the k smallest make_key(sum of the column's minima, label)
+void launch_multi_sum_topk(const MultiArgs& a, hipStream_t s);
+// a.run_keys -> group_keys [nq][k], score [nq][k], counts [nq] (may be null) and, read back from a.table, the matches (both null or neither):
+// bag j, slot s, vector u at k * q_off[j] + s * t_j + u
+void launch_multi_finalize(const MultiArgs& a, const int64_t* key_of_label, int64_t id_base, int64_t id_stride, int64_t* group_keys, float* score,
+                           int32_t* counts, int64_t* match_ids, float* match_dist, hipStream_t s);
 
 // ---------------------------------------------------------------- sparse-vector scan (eps_sparse_index_*; sparse.hip, plan: sparse_host.hpp)
 struct SparseVerdict {          // what sparse_validate_kernel leaves: ~0 / 0 before the launch

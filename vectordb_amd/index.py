@@ -500,6 +500,45 @@ class GpuIndex:
                                                        _ptr(ids), _ptr(dist), _ptr(gkeys), _ptr(rcounts), _ptr(gsizes), _ptr(counts)))
         return ids, dist, gkeys, rcounts, gsizes, counts
 
+    def search_multi(self, bags, k, cand_keys=None, cand_offsets=None, scratch_bytes=0, out=None):
+        """eps_index_search_multi: every query is a BAG of vectors; a group (set_groups) scores by the sum, over the bag's vectors in order, of the
+        distance to its closest visible row, and the k groups with the smallest sums are returned.  bags: a sequence of 2-D arrays, or a pair
+        (vectors [T, dim] - NumPy or a device tensor -, offsets: nq + 1 non-decreasing positions, offsets[0] = 0).  cand_keys None: every group is
+        considered; else only the groups whose int64 keys are named (NumPy or a device tensor) - one list for every bag, or with cand_offsets
+        (nq + 1 positions) bag j's list cand_keys[cand_offsets[j]:cand_offsets[j + 1]]; unknown keys are ignored, repeated ones count once.
+        Returns (group_keys int64[nq, k], score float32[nq, k], counts int32[nq], match_ids int64[k * T], match_dist float32[k * T]): ascending
+        (score, group key), counts = min(k, groups with a visible row for EVERY vector of the bag), the rest key 0 / +inf; the matches - the row
+        each vector met in each returned group, -1 / +inf where unused - are flat: multi_matches(match_ids, offsets, k, j) is bag j's [k, t_j] view.
+        scratch_bytes: a cap on the tables of one pass (0: the default).  NumPy vectors give NumPy results; device vectors give device tensors and
+        the call is asynchronous on the index's stream.  out=(group_keys, score, counts, match_ids, match_dist): caller-provided buffers, all NumPy
+        or all device."""
+        k = int(k)
+        vectors, offsets = _bags(bags, self.dim)
+        nq, T = offsets.size - 1, int(offsets[-1])
+        n_cand = 0
+        if cand_keys is not None:
+            if _is_dev(cand_keys):
+                if str(cand_keys.dtype) != "torch.int64" or cand_keys.dim() != 1 or not cand_keys.is_contiguous():
+                    raise ValueError("search_multi: device cand_keys must be a contiguous 1-D int64 tensor, got %s %s" % (cand_keys.dtype, tuple(cand_keys.shape)))
+                n_cand = cand_keys.numel()
+            else:
+                cand_keys = np.ascontiguousarray(cand_keys, np.int64).reshape(-1)
+                n_cand = cand_keys.size
+                if n_cand == 0:
+                    cand_keys = np.zeros(1, np.int64)   # (an empty list is still a list: the pointer says which form is meant)
+        if cand_offsets is not None:
+            if cand_keys is None:
+                raise ValueError("search_multi: cand_offsets without cand_keys")
+            cand_offsets = np.ascontiguousarray(np.asarray(cand_offsets.cpu() if _is_dev(cand_offsets) else cand_offsets), np.int64).reshape(-1)
+            if cand_offsets.size != nq + 1:
+                raise ValueError("search_multi: cand_offsets must hold nq + 1 = %d entries, got %d" % (nq + 1, cand_offsets.size))
+        gkeys, score, counts, mids, mdist = _results("search_multi", (("group_keys", (nq, k), "int64"), ("score", (nq, k), "float32"), ("counts", (nq,), "int32"),
+                                                                     ("match_ids", (k * T,), "int64"), ("match_dist", (k * T,), "float32")), out, vectors)
+        self._keep["multi"] = (vectors, offsets, cand_keys, cand_offsets)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_multi(self.h, _ptr(vectors) if T else None, _ptr(offsets), nq, _ptr(cand_keys), _ptr(cand_offsets), n_cand, k,
+                                                  int(scratch_bytes), _ptr(gkeys), _ptr(score), _ptr(counts), _ptr(mids), _ptr(mdist)))
+        return gkeys, score, counts, mids, mdist
+
     def groups_info(self):
         """eps_index_groups_info: {"n_groups", "largest_group", "last_engines": the engines the last search_groups ran, as names, "last_scan_queries"}"""
         g, big, scanned, engines = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
@@ -527,6 +566,31 @@ def _queries_2d(queries, dim):
             queries = queries[None, :]
     assert queries.shape[1] == dim
     return queries, queries.shape[0]
+
+
+def _bags(bags, dim):
+    """(vectors [T, dim], offsets int64[nq + 1]) as eps_index_search_multi reads them, from a pair (vectors, offsets) or a sequence of 2-D arrays"""
+    if isinstance(bags, tuple) and len(bags) == 2 and (_is_dev(bags[0]) or np.ndim(bags[1]) == 1 and np.ndim(bags[0]) == 2):
+        vectors, offsets = bags
+        offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_dev(offsets) else offsets), np.int64).reshape(-1)
+        if not _is_dev(vectors):
+            vectors = np.ascontiguousarray(vectors, np.float32).reshape(-1, dim)
+    else:
+        parts = [np.ascontiguousarray(b, np.float32).reshape(-1, dim) for b in bags]
+        offsets = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([p.shape[0] for p in parts], out=offsets[1:])
+        vectors = np.concatenate(parts) if parts else np.zeros((0, dim), np.float32)
+    if offsets.size < 1 or offsets[0] != 0 or np.any(np.diff(offsets) < 0):
+        raise ValueError("search_multi: offsets must start at 0 and not decrease")
+    if tuple(vectors.shape) != (int(offsets[-1]), dim) or (_is_dev(vectors) and (str(vectors.dtype) != "torch.float32" or not vectors.is_contiguous())):
+        raise ValueError("search_multi: vectors must be a C-contiguous float32 array of shape (%d, %d), got %s" % (int(offsets[-1]), dim, tuple(vectors.shape)))
+    return vectors, offsets
+
+
+def multi_matches(flat, offsets, k, j):
+    """bag j's [k, t_j] view of search_multi's flat match_ids / match_dist (slot s, vector u of the bag at k * offsets[j] + s * t_j + u)"""
+    lo, t = int(offsets[j]), int(offsets[j + 1]) - int(offsets[j])
+    return flat[k * lo:k * (lo + t)].reshape(k, t)
 
 
 def _check_bufs(who, bufs, one_kind=True, label="%s"):
