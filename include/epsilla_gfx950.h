@@ -34,6 +34,8 @@
  *                                   `group_size` of a grouped search; the reference has no relative
  *   eps_index_search_multi          (new) the k closest groups for a query that is itself several vectors, by the sum over them of the distance
  *                                   to the group's closest row - the late-interaction score of a chunk table; the reference has no relative
+ *   eps_index_search_diverse        (new) k rows of a flat search's fetch_k closest (or of the caller's lists) by maximal marginal relevance:
+ *                                   close to the query, far from each other; the reference has no relative
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
  *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
@@ -573,6 +575,42 @@ int32_t eps_index_search_group_rows(eps_index* h, const float* queries, int64_t 
 int32_t eps_index_search_multi(eps_index* h, const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys,
                                const int64_t* cand_offsets, int64_t n_cand, int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out,
                                int32_t* counts_out, int64_t* match_ids_out, float* match_dist_out);
+/* Diverse search: k rows per query that are close to the query but not copies of each other - greedy maximal marginal relevance (MMR) over a pool
+ * of the query's fetch_k closest rows.  Before, a caller ran eps_index_search with k = fetch_k, copied fetch_k x dim x 4 bytes of rows per query to
+ * the host and ran the loop there: the distances between the pool rows themselves are what only the index can compute without moving the rows.
+ * The rule, for query j.  Pool: P_j = the answer eps_index_search in EPS_MODE_FLAT gives for (j, k = fetch_k) - ascending (distance, id) order, the
+ * same visibility (not deleted, passing the int-column test and the installed program, `@distance` reading the exact distance), the same distance
+ * bits; p: only flat_engine is read (NULL: defaults), chosen as a search of (nq, fetch_k) would choose it, a program that reads `@distance` taking
+ * the exact stream scan; all engines return the same bits.  With cand_ids != NULL the pool is instead the answer of eps_index_search_among for the
+ * same cand_ids / cand_offsets / n_cand with k = fetch_k: one list for the batch or one per query, unknown ids ignored, a row named several times
+ * judged once (cand_ids == NULL with cand_offsets != NULL or n_cand != 0: EPS_USER_ERROR).  Pool position i is the i-th entry, d_i its distance to
+ * the query with those bits, np <= fetch_k the pool's size.
+ * Distance between pool rows: D(c, s) is, bit for bit, what eps_index_search_among returns for row c when the QUERY is row s as the index holds it
+ * (-0 as +0, any NaN as the one quiet NaN, like every distance the library returns).  The orientation is fixed: the selected row is the query
+ * side.  Visibility plays no part in D.
+ * Selection: lam = lambda, mu = 1.0f - lambda computed once in fp32.  Step 1 takes position 0; its score is lam * d_0, one rounded multiply.  After
+ * a row s is selected every unselected c updates m(c): m(c) = D(c, s) if s is the first selected row, otherwise m(c) = D(c, s) if D(c, s) < m(c) by
+ * IEEE less-than - a NaN never replaces a value and a NaN m is never replaced.  Step t >= 2 scores every unselected c as
+ * score(c) = (lam * d_c) - (mu * m(c)): two rounded multiplies and one rounded subtract, never contracted; the step takes the smallest score, scores
+ * ordered as distances are everywhere in the library (-0 equals +0, every NaN after +inf), ties to the smaller pool position.  Selection stops at
+ * min(k, np) rows.  lambda = 1 returns exactly the first k of the pool (while every m is finite: 0 * inf is a NaN score); lambda = 0 still starts at position 0.
+ * ids_out[j][t] (through eps_index_set_id_map), dist_out[j][t] = d of the row selected t-th, score_out[j][t] (may be NULL) = its score at selection
+ * as its key holds it (-0 as +0, a NaN as the quiet NaN), counts_out[j] (may be NULL) = min(k, np); rows in SELECTION order, the unused slots
+ * -1 / +inf / +inf.  queries and the outputs: host or device, the outputs all of one kind - device: on the index's stream, the caller synchronises,
+ * the call has no host sync of its own (EPS_FLAT_MFMA / _I8 keep the ones a search has); host: the call synchronises.  Host arrays are read before
+ * the call returns.  1 <= k <= fetch_k <= 1024, lambda in [0, 1] and not NaN, cand_offsets as eps_index_search_among checks it, else
+ * EPS_USER_ERROR; nq = 0: EPS_OK.  A null required buffer, outputs of mixed kinds, stale filters after an append: the errors of
+ * eps_index_search_among.  A sharded handle: EPS_DB_UNSUPPORTED_ERROR.
+ * After the pool (one page of a flat engine, or eps_index_search_among's two launches) one launch of diverse_select_kernel (csrc/diverse.hip): one
+ * workgroup of 256 threads per query holds the pool's keys, m and a mark per position in LDS, stages the row selected last in LDS as the query and
+ * strides over the pool with the flat scan's blocking.  Row reads: (min(k, np) - 1) x np x dim x 4 bytes per query, re-read every step, from L2
+ * where the pool fits - QUADRATIC in k when k follows fetch_k: k = fetch_k = 1024 at dim 768 reads 3.2 GB per query.
+ * eps_index_last_stats reports the call like a search: dist_evals = the pool phase's count + the (row, selected row) pairs given a distance,
+ * main_kernel_bits 32, main_kernel_rows = fetch_k, main_kernel_queries = nq, main_kernel_ms = the selection kernel.  Nothing a later call can
+ * observe changes. */
+int32_t eps_index_search_diverse(eps_index* h, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids,
+                                 const int64_t* cand_offsets, int64_t n_cand, const eps_search_params* p, int64_t* ids_out, float* dist_out,
+                                 float* score_out, int32_t* counts_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

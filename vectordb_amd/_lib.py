@@ -28,7 +28,7 @@ EXPORTS = [
     "eps_index_append_rows", "eps_index_attach_shard_rows", "eps_index_clone_rows", "eps_index_row_count", "eps_index_load_table", "eps_index_set_id_map", "eps_index_set_deleted",
     "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
     "eps_index_get_graph", "eps_index_save_graph", "eps_index_load_graph", "eps_index_search", "eps_index_select", "eps_index_search_range", "eps_index_search_among",
-    "eps_index_set_groups", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_groups_info",
+    "eps_index_set_groups", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse", "eps_index_groups_info",
     "eps_index_last_stats", "eps_index_kernel_times", "eps_normalize_rows", "eps_merge_topk", "eps_merge_topk_packed", "eps_set_tuning",
     "eps_merge_range", "eps_range_pack_bytes", "eps_merge_range_packed", "eps_merge_select", "eps_exchange_allgather_merge_range",
     "eps_exchange_unique_id", "eps_exchange_create", "eps_exchange_allgather_merge", "eps_exchange_times", "eps_exchange_info", "eps_exchange_last_error",
@@ -86,7 +86,7 @@ class _Synced:
     """The loaded library; calls that may consult a switch forward the environment first (see sync_tuning)."""
     _SYNC = frozenset(("eps_index_search", "eps_index_search_walk", "eps_index_build", "eps_index_knn_graph", "eps_index_link",
                        "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph",
-                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi"))
+                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse"))
 
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
@@ -224,6 +224,7 @@ def load():
     L.eps_index_search_groups.argtypes = [vp, vp, i64, i32, C.POINTER(SearchParams), i32, i32, i64, vp, vp, vp, vp]
     L.eps_index_search_group_rows.argtypes = [vp, vp, i64, i32, i32, C.POINTER(SearchParams), i32, i32, i64, vp, vp, vp, vp, vp, vp]
     L.eps_index_search_multi.argtypes = [vp, vp, vp, i64, vp, vp, i64, i32, i64, vp, vp, vp, vp, vp]
+    L.eps_index_search_diverse.argtypes = [vp, vp, i64, i32, i32, C.c_float, vp, vp, i64, C.POINTER(SearchParams), vp, vp, vp, vp]
     L.eps_index_groups_info.argtypes =[vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
     L.eps_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     L.eps_normalize_rows.argtypes = [vp, i64, i64, i32, i32, vp]

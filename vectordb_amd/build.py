@@ -11,7 +11,7 @@ OUT = os.path.join(HERE, "lib")
 OBJ = os.path.join(OUT, "obj")
 LIB = os.path.join(OUT, "libepsilla_gfx950.so")
 SOURCES = ["index.cpp", "index_calls.cpp", "c_abi.cpp", "shard_group.cpp", "exchange.cpp", "flat_kernels.hip", "traverse.hip", "mfma_filter.hip", "one_pass.hip",
-           "mirror_build.hip", "graph_build.hip", "select.hip", "range.hip", "merge_lists.hip", "among.hip", "groups.hip", "group_rows.hip", "multi.hip", "sparse.hip", "sparse_inverted.hip", "sparse_index.cpp"]
+           "mirror_build.hip", "graph_build.hip", "select.hip", "range.hip", "merge_lists.hip", "among.hip", "groups.hip", "group_rows.hip", "multi.hip", "diverse.hip", "sparse.hip", "sparse_inverted.hip", "sparse_index.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(os.path.dirname(HERE), "include")]
 

@@ -282,6 +282,11 @@ int32_t eps_index_search_multi(eps_index* h, const float* vectors, const int64_t
                                float* match_dist) {
   GUARD(h, IX(h)->search_multi(vectors, q_offsets, nq, cand_keys, cand_offsets, n_cand, k, scratch_bytes, group_keys, score, counts, match_ids, match_dist));
 }
+int32_t eps_index_search_diverse(eps_index* h, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids,
+                                 const int64_t* cand_offsets, int64_t n_cand, const eps_search_params* p, int64_t* ids, float* dist, float* score,
+                                 int32_t* counts) {
+  GUARD(h, IX(h)->search_diverse(queries, nq, k, fetch_k, lambda, cand_ids, cand_offsets, n_cand, p, ids, dist, score, counts));
+}
 int32_t eps_index_groups_info(eps_index* h, int64_t* n_groups, int64_t* largest_group, int32_t* last_engines, int64_t* last_scan_queries) {
   GUARD(h, IX(h)->groups_info(n_groups, largest_group, last_engines, last_scan_queries));
 }

@@ -128,6 +128,9 @@ class IndexBase {
   virtual int32_t search_multi(const float* vectors, const int64_t* q_offsets, int64_t nq, const int64_t* cand_keys, const int64_t* cand_offsets,
                                int64_t n_cand, int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out, int32_t* counts_out,
                                int64_t* match_ids_out, float* match_dist_out) = 0;
+  virtual int32_t search_diverse(const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids,
+                                 const int64_t* cand_offsets, int64_t n_cand, const eps_search_params* p, int64_t* ids_out, float* dist_out,
+                                 float* score_out, int32_t* counts_out) = 0;
   virtual int64_t row_count() const = 0;
   virtual int32_t last_stats(eps_search_stats* out) = 0;
   virtual int kernel_times(double* ms_out, int cap) = 0;
@@ -204,6 +207,11 @@ class Index : public IndexBase {
                        int32_t k, int64_t scratch_bytes, int64_t* group_keys_out, float* score_out, int32_t* counts_out, int64_t* match_ids_out,
                        float* match_dist_out) override;
 
+  // k rows of a query's pool - a flat search's fetch_k closest, or search_among's over the caller's lists - by maximal marginal relevance
+  // (eps_index_search_diverse; diverse.hip, layout: diverse_host.hpp)
+  int32_t search_diverse(const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids, const int64_t* cand_offsets,
+                         int64_t n_cand, const eps_search_params* p, int64_t* ids_out, float* dist_out, float* score_out, int32_t* counts_out) override;
+
   int64_t row_count() const override { return n_rows_; }
 
   // ---- used by the engine translation units
@@ -271,8 +279,12 @@ class Index : public IndexBase {
   // search_range(): survivor keys [nq][cap]; survivor counts | status | candidates re-ranked (what the host reads back); radii | fall-back query
   // numbers.  h_rng_: the page-locked side of the last two
   DevBuf rng_keys_, rng_cnt_, rng_in_;
-  // search_among(): [pair counter | offsets | a host list's ids]
+  // search_among(), search_diverse(): [pair counter | offsets | a host list's ids]; among_keys: the lists, gather and merge the two share
   DevBuf among_in_;
+  int32_t among_keys(const char* who, const float* dq, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k,
+                     int64_t longest, bool call_syncs, unsigned long long** d_evals_out);
+  // search_diverse(): the selected rows' keys [nq][k] (its pool is run_buf_, its pair counter among_in_'s)
+  DevBuf div_sel_;
   // search_among(), search_group_rows(): the pairs given a distance are counted on the device.  h_evals_: the counter's page-locked copy - the
   // call's dist_evals, read by last_stats once the call's last event has passed (evals_pending_), so that a call with device results stays
   // asynchronous

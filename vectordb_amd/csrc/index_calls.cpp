@@ -1,4 +1,4 @@
-// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, search_multi, the steps they share (their results: result_block.hpp), and the read-out of their statistics.
+// The serving calls of Index (see index.hpp): flat_stream, search, select, search_range, search_among, search_groups, search_group_rows, search_multi, search_diverse, the steps they share (their results: result_block.hpp), and the read-out of their statistics.
 #include "index.hpp"
 
 #include <algorithm>
@@ -465,54 +465,31 @@ int32_t Index::search_range(const float* queries, int64_t nq, const float* radiu
 }
 
 // ------------------------------------------------------------------------------------------------ search_among
-// The k closest visible rows among the ids the caller names (among.hip): gather, merge, result conversion - no host sync of its own, so a call
-// with device results stays asynchronous (the pairs given a distance are counted on the device and read by last_stats).  Reports like a search
-// (statistics, kernel ring); changes nothing a later search can observe.
-int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k, int64_t* ids,
-                            float* dist, int32_t* counts) {
-  if (k < 1 || k > AMONG_MAX_K) return fail(EPS_USER_ERROR, "search_among: k must be in [1, 1024]");
-  HIP_TRY(hipSetDevice(device_));
-  if (cand_offsets && is_device_ptr(cand_offsets)) return fail(EPS_USER_ERROR, "search_among: cand_offsets must be a host array");
-  const char* why;
-  int64_t longest = 0;
-  if (among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_among: ") + why);
-  if (nq == 0) return EPS_OK;
-  if (!queries || !ids || !dist || (n_cand > 0 && !cand_ids)) return fail(EPS_USER_ERROR, "search_among: null buffer");
-  ResultBlock rb;
-  const auto r_ids = rb.add(ids, (size_t)nq * k);
-  const auto r_dist = rb.add(dist, (size_t)nq * k);
-  const auto r_cnt = rb.add(counts, (size_t)nq);
-  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search_among: ids_out, dist_out and counts_out must all be host or all be device pointers");
-  const bool out_dev = rb.device();
-  int32_t rc = check_filters_cover_table("search_among");
-  if (rc != EPS_OK) return rc;
-  begin_timed_call();
-  prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
-
-  const float* dq;
-  rc = stage_queries("search_among", queries, nq, &dq, !out_dev);
-  if (rc != EPS_OK) return rc;
-
-  // ---- scratch: [pair counter | offsets | a host list's ids], partial lists, result keys, host results' device block
+// The middle of search_among, and the pool of search_diverse's candidate form, after their checks and begin_timed_call: the lists to the device,
+// gather, merge - query j's k smallest unique keys over the visible rows its list names in run_buf_[j][k], the call's first event (ev0_) on the
+// stream, the pairs' counter cleared (*d_evals_out: the caller publishes it).  longest: as among_lists_check left it
+int32_t Index::among_keys(const char* who, const float* dq, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k,
+                          int64_t longest, bool call_syncs, unsigned long long** d_evals_out) {
+  // ---- scratch: [pair counter | offsets | a host list's ids], partial lists, result keys
   const bool ids_dev = n_cand > 0 && is_device_ptr(cand_ids);
   const size_t off_bytes = cand_offsets ? (size_t)(nq + 1) * sizeof(int64_t) : 0, list_bytes = ids_dev ? 0 : (size_t)n_cand * sizeof(int64_t);
   const AmongPlan plan = among_plan(!cand_offsets, nq, longest, k, pick_nq(nq, k, (int)dim_));
   if (!among_in_.reserve(8 + off_bytes + list_bytes) || !partial_buf_.reserve((size_t)nq * plan.W * k * sizeof(u64)) ||
-      !run_buf_.reserve((size_t)nq * k * sizeof(u64)) || !rb.place(out_block_))
-    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of device memory (scratch)");
-  if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of page-locked host memory");
-  unsigned long long* d_evals = among_in_.as<unsigned long long>();
+      !run_buf_.reserve((size_t)nq * k * sizeof(u64)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of device memory (scratch)");
+  if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, std::string(who) + ": out of page-locked host memory");
+  unsigned long long* d_evals = *d_evals_out = among_in_.as<unsigned long long>();
   int64_t* d_off = cand_offsets ? among_in_.as<int64_t>() + 1 : nullptr;
   const int64_t* d_list = cand_ids;
-  rc = clear_device_evals(d_evals);
+  int32_t rc = clear_device_evals(d_evals);
   if (rc != EPS_OK) return rc;
   if (cand_offsets) {
-    rc = copy_host_in(d_off, cand_offsets, off_bytes, !out_dev);
+    rc = copy_host_in(d_off, cand_offsets, off_bytes, call_syncs);
     if (rc != EPS_OK) return rc;
   }
   if (!ids_dev && n_cand > 0) {
     d_list = reinterpret_cast<const int64_t*>(among_in_.as<char>() + 8 + off_bytes);
-    rc = copy_host_in(const_cast<int64_t*>(d_list), cand_ids, list_bytes, !out_dev);
+    rc = copy_host_in(const_cast<int64_t*>(d_list), cand_ids, list_bytes, call_syncs);
     if (rc != EPS_OK) return rc;
   }
   u64* run_keys = run_buf_.as<u64>();
@@ -545,8 +522,134 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   } else {
     launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
   }
+  return EPS_OK;
+}
+
+// The k closest visible rows among the ids the caller names (among.hip): gather, merge, result conversion - no host sync of its own, so a call
+// with device results stays asynchronous (the pairs given a distance are counted on the device and read by last_stats).  Reports like a search
+// (statistics, kernel ring); changes nothing a later search can observe.
+int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* cand_ids, const int64_t* cand_offsets, int64_t n_cand, int32_t k, int64_t* ids,
+                            float* dist, int32_t* counts) {
+  if (k < 1 || k > AMONG_MAX_K) return fail(EPS_USER_ERROR, "search_among: k must be in [1, 1024]");
+  HIP_TRY(hipSetDevice(device_));
+  if (cand_offsets && is_device_ptr(cand_offsets)) return fail(EPS_USER_ERROR, "search_among: cand_offsets must be a host array");
+  const char* why;
+  int64_t longest = 0;
+  if (among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_among: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (!queries || !ids || !dist || (n_cand > 0 && !cand_ids)) return fail(EPS_USER_ERROR, "search_among: null buffer");
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr)) return fail(EPS_USER_ERROR, "search_among: ids_out, dist_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
+  int32_t rc = check_filters_cover_table("search_among");
+  if (rc != EPS_OK) return rc;
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the candidate's exact distance)
+
+  const float* dq;
+  rc = stage_queries("search_among", queries, nq, &dq, !out_dev);
+  if (rc != EPS_OK) return rc;
+
+  if (!rb.place(out_block_)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_among: out of device memory (scratch)");
+  unsigned long long* d_evals = nullptr;
+  rc = among_keys("search_among", dq, nq, cand_ids, cand_offsets, n_cand, k, longest, !out_dev, &d_evals);
+  if (rc != EPS_OK) return rc;
+  const u64* run_keys = run_buf_.as<u64>();
   launch_finalize(run_keys, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_cnt), stream_);
   rc = publish_device_evals(d_evals);
+  if (rc != EPS_OK) return rc;
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(rb);
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ search_diverse
+// k rows of every query's pool by maximal marginal relevance (diverse.hip, layout: diverse_host.hpp).  The pool - fetch_k keys per query in
+// run_buf_ - is one page of the flat engine a search of (nq, fetch_k) would take, or search_among's gather and merge over the caller's lists; then
+// one launch of the selection kernel and the result conversion.  No host sync of its own (the matrix engine keeps the ones a search has).  Reports
+// like a search; changes nothing a later call can observe.
+int32_t Index::search_diverse(const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids, const int64_t* cand_offsets,
+                              int64_t n_cand, const eps_search_params* pp, int64_t* ids, float* dist, float* score, int32_t* counts) {
+  const eps_search_params p = search_params_or_default(pp);
+  const char* why;
+  if (diverse_args_check(nq, k, fetch_k, lambda, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_diverse: ") + why);
+  if (!flat_engine_known(p.flat_engine)) return fail(EPS_USER_ERROR, "search_diverse: unknown flat engine");
+  HIP_TRY(hipSetDevice(device_));
+  const bool cand = cand_ids != nullptr;
+  if (!cand && (cand_offsets || n_cand != 0)) return fail(EPS_USER_ERROR, "search_diverse: null buffer");   // (a list without its ids)
+  if (cand_offsets && is_device_ptr(cand_offsets)) return fail(EPS_USER_ERROR, "search_diverse: cand_offsets must be a host array");
+  int64_t longest = 0;
+  if (cand && among_lists_check(cand_offsets, nq, n_cand, &longest, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_diverse: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (!queries || !ids || !dist) return fail(EPS_USER_ERROR, "search_diverse: null buffer");
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_score = rb.add(score, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr))
+    return fail(EPS_USER_ERROR, "search_diverse: ids_out, dist_out, score_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
+  int32_t rc = check_filters_cover_table("search_diverse");
+  if (rc != EPS_OK) return rc;
+  begin_timed_call();
+  prefilter_call_ = false;   // (@distance reads the row's exact distance)
+
+  const float* dq;
+  rc = stage_queries("search_diverse", queries, nq, &dq, !out_dev);
+  if (rc != EPS_OK) return rc;
+  if (!div_sel_.reserve((size_t)nq * k * sizeof(u64)) || !rb.place(out_block_))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_diverse: out of device memory (scratch)");
+
+  // ---- the pool: run_buf_[nq][fetch_k], ascending keys, KEY_EMPTY behind them
+  unsigned long long* d_evals = nullptr;
+  if (cand) {
+    rc = among_keys("search_diverse", dq, nq, cand_ids, cand_offsets, n_cand, fetch_k, longest, !out_dev, &d_evals);
+    if (rc != EPS_OK) return rc;
+  } else {
+    if (!among_in_.reserve(8) || !run_buf_.reserve((size_t)nq * fetch_k * sizeof(u64)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_diverse: out of device memory (scratch)");
+    if (!h_evals_.reserve(8)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_diverse: out of page-locked host memory");
+    d_evals = among_in_.as<unsigned long long>();
+    rc = clear_device_evals(d_evals);
+    if (rc != EPS_OK) return rc;
+    HIP_TRY(hipEventRecord(ev0_, stream_));
+    // the flat engine a search of (nq, fetch_k) would take; all of them carry the stream scan's bits
+    const FlatChoice fc = resolve_flat_engine(p.flat_engine, nq, fetch_k, false);
+    // (a filter on @distance needs exact distances where it is evaluated; an empty table: the stream page's fill)
+    const bool matrix = fc.matrix && !(prog_len_ > 0 && prog_uses_dist_) && n_rows_ > 0;
+    rc = matrix ? flat_mfma_search(*this, dq, nq, fetch_k, run_buf_.as<u64>(), false, fc.bits)
+                : flat_stream_page(dq, nq, fetch_k, 0, n_rows_, run_buf_.as<u64>(), -1, true, nullptr, 0);
+    if (rc != EPS_OK) return rc;
+  }
+
+  DiverseArgs a;
+  a.rows = d_rows_;
+  a.dim = (int)dim_;
+  a.metric = metric_;
+  a.pool = run_buf_.as<u64>();
+  a.nq = nq;
+  a.fetch_k = fetch_k;
+  a.k = k;
+  a.lam = lambda;
+  a.mu = 1.0f - lambda;
+  a.sel_keys = div_sel_.as<u64>();
+  a.score = rb.dev(r_score);
+  a.evals = d_evals;
+  HIP_TRY(hipEventRecord(evk0_, stream_));
+  launch_diverse_select(a, stream_);
+  HIP_TRY(hipEventRecord(evk1_, stream_));
+  set_main_kernel(1, fetch_k, nq, 32);
+  launch_finalize(a.sel_keys, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_cnt), stream_);
+  rc = publish_device_evals(d_evals);   // (the pool's and the selection's pairs: last_stats adds them)
   if (rc != EPS_OK) return rc;
   HIP_TRY(hipEventRecord(ev1_, stream_));
   if (!out_dev) {

@@ -6,6 +6,7 @@
 
 #include "among_host.hpp"
 #include "device_common.hpp"
+#include "diverse_host.hpp"
 #include "group_rows_host.hpp"
 #include "groups_host.hpp"
 #include "merge_host.hpp"
@@ -315,6 +316,21 @@ void launch_multi_sum_topk(const MultiArgs& a, hipStream_t s);
 // bag j, slot s, vector u at k * q_off[j] + s * t_j + u
 void launch_multi_finalize(const MultiArgs& a, const int64_t* key_of_label, int64_t id_base, int64_t id_stride, int64_t* group_keys, float* score,
                            int32_t* counts, int64_t* match_ids, float* match_dist, hipStream_t s);
+
+// ---------------------------------------------------------------- diverse search (eps_index_search_diverse; diverse.hip, layout: diverse_host.hpp)
+struct DiverseArgs {
+  const float* rows;
+  int dim, metric;
+  const u64* pool;             // [nq][fetch_k] every query's pool: ascending keys, KEY_EMPTY behind them
+  int64_t nq;
+  int fetch_k, k;
+  float lam, mu;               // lambda, and 1.0f - lambda as the host rounded it
+  u64* sel_keys;               // [nq][k] the pool keys of the selected rows in selection order, KEY_EMPTY behind them
+  float* score;                // [nq][k] their scores at selection, +inf behind them; may be null
+  unsigned long long* evals;   // (row, selected row) pairs given a distance, added to
+};
+// one workgroup per query (in slices of DIVERSE_GRID queries): the greedy selection over the pool
+void launch_diverse_select(const DiverseArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- sparse-vector scan (eps_sparse_index_*; sparse.hip, plan: sparse_host.hpp)
 struct SparseVerdict {          // what sparse_validate_kernel leaves: ~0 / 0 before the launch

@@ -385,6 +385,10 @@ class ShardGroup : public IndexBase {
                        float*) override {
     return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
   }
+  int32_t search_diverse(const float*, int64_t, int32_t, int32_t, float, const int64_t*, const int64_t*, int64_t, const eps_search_params*, int64_t*, float*,
+                         float*, int32_t*) override {
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the diverse search serves single-device indices only (a sharded table is not served)");
+  }
   int32_t groups_info(int64_t*, int64_t*, int32_t*, int64_t*) override {
     return fail(EPS_DB_UNSUPPORTED_ERROR, "sharded index: the grouped search serves single-device indices only (a sharded table is not served)");
   }

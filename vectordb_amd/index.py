@@ -446,6 +446,42 @@ class GpuIndex:
                                                   _ptr(dist), _ptr(counts)))
         return out_ids, dist, counts
 
+    def search_diverse(self, queries, k, fetch_k, lam=0.5, ids=None, offsets=None, flat_engine="auto", out=None):
+        """eps_index_search_diverse: per query k rows of its pool by greedy maximal marginal relevance - step 1 takes the closest row, every later
+        step the unselected row with the smallest lam * d(row, query) - (1 - lam) * min over the selected rows s of D(row, s), ties to the earlier pool
+        position.  The pool is search(k=fetch_k)'s answer (flat mode, flat_engine as for search_range: the same bits from all of them) or, with ids
+        given, search_among(ids, fetch_k, offsets)'s - ids and offsets as search_among takes them.  Returns (ids int64[nq, k], dist float32[nq, k],
+        score float32[nq, k], counts int32[nq]) in SELECTION order, counts = min(k, pool size), the rest -1 / +inf / +inf; dist are a flat search's
+        bits, lam = 1 returns the pool's first k.  1 <= k <= fetch_k <= 1024; the selection reads (k - 1) x pool x dim x 4 bytes per query: quadratic
+        when k follows fetch_k.  NumPy queries give NumPy results; device queries give device tensors and the call is asynchronous on the index's
+        stream.  out=(ids, dist, score, counts): caller-provided buffers, all NumPy or all device."""
+        k, fetch_k = int(k), int(fetch_k)
+        queries, nq = _queries_2d(queries, self.dim)
+        n_cand = 0
+        if ids is None:
+            if offsets is not None:
+                raise ValueError("search_diverse: offsets without ids")
+        elif _is_dev(ids):
+            if str(ids.dtype) != "torch.int64" or ids.dim() != 1 or not ids.is_contiguous():
+                raise ValueError("search_diverse: device ids must be a contiguous 1-D int64 tensor, got %s %s" % (ids.dtype, tuple(ids.shape)))
+            n_cand = ids.numel()
+        else:
+            ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            n_cand = ids.size
+        if ids is not None and n_cand == 0:
+            ids = np.zeros(1, np.int64)   # (an empty list is still a list: a non-null pointer that is never read)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_dev(offsets) else offsets), np.int64).reshape(-1)
+            if offsets.size != nq + 1:
+                raise ValueError("search_diverse: offsets must hold nq + 1 = %d entries, got %d" % (nq + 1, offsets.size))
+        out_ids, dist, score, counts = _results("search_diverse", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("score", (nq, k), "float32"),
+                                                                   ("counts", (nq,), "int32")), out, queries)
+        p = self.params(flat_engine=RANGE_ENGINES[flat_engine])
+        self._keep["diverse"] = (queries, ids, offsets)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_diverse(self.h, _ptr(queries), nq, k, fetch_k, float(lam), _ptr(ids), _ptr(offsets), n_cand, C.byref(p),
+                                                    _ptr(out_ids), _ptr(dist), _ptr(score), _ptr(counts)))
+        return out_ids, dist, score, counts
+
     def set_groups(self, keys):
         """eps_index_set_groups: one int64 key per row (NumPy, or a contiguous 1-D int64 device tensor); rows with equal keys form a group.  None
         forgets the groups.  After attach_rows / append_rows the keys must be set again."""
