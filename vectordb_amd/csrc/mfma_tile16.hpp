@@ -16,8 +16,13 @@
 //     in the NEXT step's first sub-step (from the previous step's cursor), and the step's closing wait is vmcnt(12) - those four have landed.
 //   * A lane's four accumulators of a block are four consecutive rows: the block's start values are one ds_read_b128, and the first sub-step's
 //     MFMAs of a tile take it as their C operand (D != C) for all four query blocks - no moves, no initialisation pass.
-//   * Epilogue: four running maxima (one per query block) over the 16 row blocks, four compares, one vote and one branch per tile; a tile that
-//     passes walks the hit query blocks' row blocks: block maximum, 4-bit mask, bits.
+//   * Epilogue, after the last K-step (no MFMA in flight): per query block four group maxima (row blocks 4 g .. 4 g + 3, eight v_max3_i32 each; the
+//     last group reads blocks 14 and 15 out of the accumulator file inside its chain) and their maximum, four compares, one vote and one branch per
+//     tile.  The 16 group maxima stay alive to the end of the tile, never across the K loop.  A tile that passes walks, per hit query block, only the
+//     groups whose maximum passes (one vote each), and in them the row blocks: block maximum, 4-bit mask, bits.
+//     profiles/r17_filter_epilogue.txt: the narrowed walk is worth 1.2-1.8 % of the headline step.  Folding the finished row blocks into the
+//     maxima in the issue slots of the tile's last sub-step (two v_max3_i32 behind each MFMA, thresholds read there too) was built and measured
+//     beside it: 0.1 %, inside the noise - the step waits for the wavefront with the hit, not for the common path - and is not in this file.
 // Query operand: a.qf here is the 16x16x64 fragment-major copy, [b_pad/16][d_pad8/64][64 lanes][16 bytes]: lane l = query l % 16, bytes
 // 16 (l / 16) .. + 16 of a K = 64 piece (query_prep8_kernel writes it beside the 32x32x32 copy; launch_filter hands it to this form only).
 #pragma once
@@ -44,6 +49,31 @@ __device__ __forceinline__ int max16i4(const i32x4& p, const i32x4& q, const i32
       : "=&v"(d)
       : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]), "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(t[0]),
         "v"(t[1]), "v"(t[2]), "v"(t[3]));
+  return d;
+}
+// the same with r and t in the accumulator file (row blocks >= V16_VB): read through two temporaries inside the chain, so that the eight values
+// are not all copied to arch VGPRs beforehand (32 registers per tile that hipcc makes room for by parking others in the accumulator file)
+__device__ __forceinline__ int max16i4_acc(const i32x4& p, const i32x4& q, const i32x4& r, const i32x4& t) {
+  int d, x, y;
+  asm("v_max3_i32 %0, %3, %4, %5\n\t"
+      "v_max3_i32 %0, %0, %6, %7\n\t"
+      "v_max3_i32 %0, %0, %8, %9\n\t"
+      "v_accvgpr_read_b32 %1, %11\n\t"
+      "v_max3_i32 %0, %0, %10, %1\n\t"
+      "v_accvgpr_read_b32 %1, %12\n\t"
+      "v_accvgpr_read_b32 %2, %13\n\t"
+      "v_max3_i32 %0, %0, %1, %2\n\t"
+      "v_accvgpr_read_b32 %1, %14\n\t"
+      "v_accvgpr_read_b32 %2, %15\n\t"
+      "v_max3_i32 %0, %0, %1, %2\n\t"
+      "v_accvgpr_read_b32 %1, %16\n\t"
+      "v_accvgpr_read_b32 %2, %17\n\t"
+      "v_max3_i32 %0, %0, %1, %2\n\t"
+      "v_accvgpr_read_b32 %1, %18\n\t"
+      "v_max_i32 %0, %0, %1"
+      : "=&v"(d), "=&v"(x), "=&v"(y)
+      : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]), "a"(r[0]), "a"(r[1]), "a"(r[2]), "a"(r[3]), "a"(t[0]),
+        "a"(t[1]), "a"(t[2]), "a"(t[3]));
   return d;
 }
 constexpr int V16_VB = 14;   // row blocks (of 16) whose accumulators live in arch VGPRs: 224 registers, as V7_VI = 7 blocks of 32
@@ -386,12 +416,16 @@ __device__ __forceinline__ void v7_tile16_ids(const FilterArgs& a) {
     for (int j = 0; j < NJ; ++j) Tq[j] = __builtin_bit_cast(int, tq_lds[j * 64 + lne]);
     // common path: one running maximum per query block over the tile's 16 row blocks, as v_max3_i32 chains of four blocks each (asm: as C++ the
     // pair maxima are shared with the hit path below and kept alive for it - a hundred registers parked in the accumulator file per tile)
-    int mx[NJ];
+    // The four group maxima of a query block (row blocks 4 g .. 4 g + 3) stay alive until the hit path has used them: 16 registers, from here
+    // to the end of the tile only - never across the K loop.
+    int mx[NJ], gm[NJ][4];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int g0 = max16i4(acc[0][j], acc[1][j], acc[2][j], acc[3][j]), g1 = max16i4(acc[4][j], acc[5][j], acc[6][j], acc[7][j]);
-      const int g2 = max16i4(acc[8][j], acc[9][j], acc[10][j], acc[11][j]), g3 = max16i4(acc[12][j], acc[13][j], acc[14][j], acc[15][j]);
-      mx[j] = max(max(g0, g1), max(g2, g3));
+#pragma unroll
+      for (int g = 0; g < 3; ++g) gm[j][g] = max16i4(acc[4 * g][j], acc[4 * g + 1][j], acc[4 * g + 2][j], acc[4 * g + 3][j]);
+      static_assert(VB == NB - 2, "the last group: two blocks in arch VGPRs, two in the accumulator file");
+      gm[j][3] = max16i4_acc(acc[12][j], acc[13][j], acc[14][j], acc[15][j]);
+      mx[j] = max(max(gm[j][0], gm[j][1]), max(gm[j][2], gm[j][3]));
     }
     const bool h = (mx[0] >= Tq[0]) | (mx[1] >= Tq[1]) | (mx[2] >= Tq[2]) | (mx[3] >= Tq[3]);
     if (__builtin_expect(__any(h), 0)) {
@@ -404,23 +438,28 @@ __device__ __forceinline__ void v7_tile16_ids(const FilterArgs& a) {
         if (!__any(mx[j] >= Tq[j])) continue;
         const int64_t qq = qbase + j * 16 + (lh & 15);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          __builtin_amdgcn_sched_barrier(0);   // one block at a time
-          const int bm = max(max(acc[i][j][0], acc[i][j][1]), max(acc[i][j][2], acc[i][j][3]));
-          if (!__any(bm >= Tq[j])) continue;
-          u32 hm = 0;
+        for (int g = 0; g < 4; ++g) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (!__any(gm[j][g] >= Tq[j])) continue;   // only the groups of four row blocks that hold a passing row are walked
 #pragma unroll
-          for (int r = 0; r < 4; ++r) hm |= acc[i][j][r] >= Tq[j] ? (1u << r) : 0u;
-          if (qq >= a.nq) hm = 0;
-          while (hm) {
-            const int r = __builtin_ctz(hm);
-            hm &= hm - 1;
-            const int64_t row64 = row0 + i * 16 + rl + r;
-            if (row64 >= a.row_hi) continue;       // (rows beyond the stage's last row: the tile that crosses it)
-            const u32 row = (u32)row64;
-            const u32 e = atomicAdd(wcnt, 1u);   // LDS: no VMEM counter involved
-            if (e < (u32)V7_CAPW) wbuf[e] = ((u64)qq << 32) | row;
-            else append(qq, row);
+          for (int i = 4 * g; i < 4 * g + 4; ++i) {
+            __builtin_amdgcn_sched_barrier(0);   // one block at a time
+            const int bm = max(max(acc[i][j][0], acc[i][j][1]), max(acc[i][j][2], acc[i][j][3]));
+            if (!__any(bm >= Tq[j])) continue;
+            u32 hm = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hm |= acc[i][j][r] >= Tq[j] ? (1u << r) : 0u;
+            if (qq >= a.nq) hm = 0;
+            while (hm) {
+              const int r = __builtin_ctz(hm);
+              hm &= hm - 1;
+              const int64_t row64 = row0 + i * 16 + rl + r;
+              if (row64 >= a.row_hi) continue;       // (rows beyond the stage's last row: the tile that crosses it)
+              const u32 row = (u32)row64;
+              const u32 e = atomicAdd(wcnt, 1u);   // LDS: no VMEM counter involved
+              if (e < (u32)V7_CAPW) wbuf[e] = ((u64)qq << 32) | row;
+              else append(qq, row);
+            }
           }
         }
       }
