@@ -611,6 +611,46 @@ int32_t eps_index_search_multi(eps_index* h, const float* vectors, const int64_t
 int32_t eps_index_search_diverse(eps_index* h, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids,
                                  const int64_t* cand_offsets, int64_t n_cand, const eps_search_params* p, int64_t* ids_out, float* dist_out,
                                  float* score_out, int32_t* counts_out);
+/* Search under per-query filters: a batch in which every query carries its own WHERE - the multi-tenant / per-user case.  Before, a caller ran, per
+ * program, eps_index_set_filter_program_ex + eps_index_search over that program's queries: P uploads, P evaluations of a program over all n
+ * attribute rows, P small searches.  Here the attribute rows are judged once for all programs and every query scans only what its program shows.
+ * Inputs.  ops[prog_offsets[j] .. prog_offsets[j + 1]) is program j (eps_filter_op, the limits of eps_index_set_filter_program: 64 instructions,
+ * stack depth 16); prog_offsets is a HOST int32[n_progs + 1] from 0, non-decreasing; 1 <= n_progs <= 64; an empty program passes every row.
+ * query_prog is a HOST int32[nq]: the program of each query, in any order; a program may have no query.  rows / stride_bytes / n_rows / flags: the
+ * packed attribute rows, read as eps_index_set_filter_program_ex reads them - host (copied; EPS_FILTER_ROWS_APPEND_ONLY: only the tail beyond what
+ * this pointer handed over before; the installed program's device copy is used where it mirrors the same host table under that flag) or device
+ * (in place), rows = NULL: the rows eps_index_load_table kept.  n_rows must equal eps_index_row_count.
+ * The rule.  Query q sees row r iff r is visible under the index's standing state (not deleted, passing the int-column test and the installed
+ * program) AND program query_prog[q] leaves a non-zero value on r.  The answer is the k smallest (distance, id) keys over those rows; the
+ * distances are, bit for bit, what eps_index_search in EPS_MODE_FLAT returns for that (row, query).  ids_out [nq][k] (through eps_index_set_id_map),
+ * dist_out [nq][k], unused slots -1 / +inf; counts_out [nq] (may be NULL) = min(k, visible); visible_out [nq] (may be NULL) = the rows q's filter
+ * leaves visible.  queries and the outputs: host or device as for eps_index_search, the outputs all of one kind.
+ * engine.  EPS_FILTERS_LISTS: after the verdict pass (one thread per row runs every distinct program - programs with identical instructions are
+ * judged once - and ballots each verdict into a bit plane per program, bit set = hidden) and ONE host sync that reads every plane's visible count,
+ * the visible rows of a plane are written as a list of u32 row numbers and gathered: a workgroup stages up to 4 queries of one plane and walks the
+ * list with the flat scan's arithmetic - count_j x dim x 4 bytes of rows per 4 queries of program j, no visibility test in the loop.
+ * EPS_FILTERS_PLANES: after the same pass and sync, per program with a query the flat search p->flat_engine selects runs over that program's
+ * queries with the plane in the deleted bitset's place - a loop of existing launches, which gives the matrix engine to filters that hide little.
+ * EPS_FILTERS_AUTO: per program - planes where the flat engine would be the matrix engine and the program is dense (visible share x sqrt(blocks
+ * of 4 queries) > 0.4: the measured break-even of DESIGN 5.13), or where the lists no longer fit 256 MiB; lists otherwise.  All engines return the same ids and bits wherever the flat engines themselves do.
+ * Refusals, EPS_USER_ERROR: k outside [1, 1024], a query_prog entry outside [0, n_progs), a malformed prog_offsets, a malformed program, a program
+ * that pushes `@distance` or an installed program that reads it (a plane is computed before any distance exists), n_rows != eps_index_row_count,
+ * stale standing filters after an append, outputs of mixed kinds, a null required buffer.  A program of more than 64 instructions and a sharded
+ * handle: EPS_DB_UNSUPPORTED_ERROR.  nq = 0: EPS_OK.  No ANSWER of a later call changes: the installed program, bitset and column stay.  The plane
+ * engine's searches are searches: they move the matrix engine's adaptive state (mirror built, 8-bit pass trusted or declined) as any search
+ * does, so a later search may take another, still exact, path; and each of them overwrites main_kernel_* before the gather, if any, does.
+ * eps_index_last_stats reports the call like a search: dist_evals = sum over list-engine programs of visible rows x queries + what the plane
+ * engine's searches count; main_kernel_* = the gather (bits 32, rows = list entries, queries = those on the list engine) where it ran, else the
+ * last plane search's.  eps_index_filters_info: the last call's engine per program (0: no query) and visible rows per program, the first
+ * min(cap, n_progs) of them (either array may be NULL); *n_progs_out = n_progs. */
+#define EPS_FILTERS_AUTO 0
+#define EPS_FILTERS_LISTS 1
+#define EPS_FILTERS_PLANES 2
+int32_t eps_index_search_filters(eps_index* h, const float* queries, int64_t nq, int32_t k, const eps_search_params* p, const eps_filter_op* ops,
+                                 const int32_t* prog_offsets, int32_t n_progs, const int32_t* query_prog, const void* rows, int64_t stride_bytes,
+                                 int64_t n_rows, int32_t flags, int32_t engine, int64_t* ids_out, float* dist_out, int32_t* counts_out,
+                                 int64_t* visible_out);
+int32_t eps_index_filters_info(eps_index* h, int32_t* engines_out, int64_t* visible_out, int32_t cap, int32_t* n_progs_out);
 int32_t eps_index_last_stats(const eps_index* h, eps_search_stats* out);
 /* main-kernel milliseconds (hipEvent pairs recorded on the index's stream) of the most recent search calls, oldest
  * first, at most min(cap, 64); synchronises the stream.  Returns the number written.  Lets a caller time a run of

@@ -20,6 +20,8 @@ METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_DOT_PRODUCT = 0, 1, 2
 MODE_REFERENCE, MODE_FLAT, MODE_GRAPH = 0, 1, 2
 FLAT_AUTO, FLAT_STREAM, FLAT_MFMA, FLAT_MFMA_I8 = 0, 1, 2, 3
 FILTER_ROWS_APPEND_ONLY = 1
+FILTERS_AUTO, FILTERS_LISTS, FILTERS_PLANES = 0, 1, 2
+FILTERS_MAX_PROGS = 64
 OPS = {None: 0, "": 0, "<": 1, "<=": 2, "==": 3, "=": 3, ">=": 4, ">": 5, "!=": 6, "<>": 6}
 
 EXPORTS = [
@@ -27,7 +29,7 @@ EXPORTS = [
     "eps_index_last_error", "eps_index_last_error_class", "eps_index_set_stream", "eps_index_synchronize", "eps_index_attach_rows",
     "eps_index_append_rows", "eps_index_attach_shard_rows", "eps_index_clone_rows", "eps_index_row_count", "eps_index_load_table", "eps_index_set_id_map", "eps_index_set_deleted",
     "eps_index_set_int_filter", "eps_index_set_filter_program", "eps_index_set_filter_program_ex", "eps_index_search_walk", "eps_index_select_edges", "eps_index_inter_insert", "eps_index_knn_graph", "eps_index_link", "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_build", "eps_index_set_graph", "eps_index_graph_info",
-    "eps_index_get_graph", "eps_index_save_graph", "eps_index_load_graph", "eps_index_search", "eps_index_select", "eps_index_search_range", "eps_index_search_among",
+    "eps_index_get_graph", "eps_index_save_graph", "eps_index_load_graph", "eps_index_search", "eps_index_select", "eps_index_search_range", "eps_index_search_among", "eps_index_search_filters", "eps_index_filters_info",
     "eps_index_set_groups", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse", "eps_index_groups_info",
     "eps_index_last_stats", "eps_index_kernel_times", "eps_normalize_rows", "eps_merge_topk", "eps_merge_topk_packed", "eps_set_tuning",
     "eps_merge_range", "eps_range_pack_bytes", "eps_merge_range_packed", "eps_merge_select", "eps_exchange_allgather_merge_range",
@@ -86,7 +88,7 @@ class _Synced:
     """The loaded library; calls that may consult a switch forward the environment first (see sync_tuning)."""
     _SYNC = frozenset(("eps_index_search", "eps_index_search_walk", "eps_index_build", "eps_index_knn_graph", "eps_index_link",
                        "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph",
-                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse"))
+                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse", "eps_index_search_filters"))
 
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
@@ -220,6 +222,8 @@ def load():
     L.eps_index_select.argtypes = [vp, i64, i64, vp, vp, vp]
     L.eps_index_search_range.argtypes = [vp, vp, i64, vp, i32, C.POINTER(SearchParams), vp, vp, vp, vp]
     L.eps_index_search_among.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
+    L.eps_index_search_filters.argtypes = [vp, vp, i64, i32, C.POINTER(SearchParams), C.POINTER(FilterOp), vp, i32, vp, vp, i64, i64, i32, i32, vp, vp, vp, vp]
+    L.eps_index_filters_info.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
     L.eps_index_set_groups.argtypes = [vp, vp, i64]
     L.eps_index_search_groups.argtypes = [vp, vp, i64, i32, C.POINTER(SearchParams), i32, i32, i64, vp, vp, vp, vp]
     L.eps_index_search_group_rows.argtypes = [vp, vp, i64, i32, i32, C.POINTER(SearchParams), i32, i32, i64, vp, vp, vp, vp, vp, vp]

@@ -267,6 +267,16 @@ int32_t eps_index_search_among(eps_index* h, const float* q, int64_t nq, const i
   return on_single_device(h, "search_among: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER,
                           [&](Index& ix) { return ix.search_among(q, nq, cand_ids, cand_offsets, n_cand, k, ids, dist, counts); });
 }
+int32_t eps_index_search_filters(eps_index* h, const float* q, int64_t nq, int32_t k, const eps_search_params* p, const eps_filter_op* ops,
+                                 const int32_t* prog_offsets, int32_t n_progs, const int32_t* query_prog, const void* rows, int64_t stride_bytes,
+                                 int64_t n_rows, int32_t flags, int32_t engine, int64_t* ids, float* dist, int32_t* counts, int64_t* visible) {
+  return on_single_device(h, "search_filters: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    return ix.search_filters(q, nq, k, p, ops, prog_offsets, n_progs, query_prog, rows, stride_bytes, n_rows, flags, engine, ids, dist, counts, visible);
+  });
+}
+int32_t eps_index_filters_info(eps_index* h, int32_t* engines, int64_t* visible, int32_t cap, int32_t* n_progs) {
+  return on_single_device(h, "filters_info: single-device indices only", EPS_ERRCLASS_OTHER, [&](Index& ix) { return ix.filters_info(engines, visible, cap, n_progs); });
+}
 int32_t eps_index_set_groups(eps_index* h, const int64_t* keys, int64_t n) { GUARD(h, IX(h)->set_groups(keys, n)); }
 int32_t eps_index_search_groups(eps_index* h, const float* q, int64_t nq, int32_t k, const eps_search_params* p, int32_t engine, int32_t page_rows,
                                 int64_t scratch_bytes, int64_t* ids, float* dist, int64_t* group_keys, int32_t* counts) {

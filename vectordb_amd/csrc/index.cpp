@@ -476,26 +476,9 @@ int32_t Index::set_filter_program_pitched(const eps_filter_op* ops, int32_t nops
   if ((!rows && !use_loaded) || stride <= 0 || n_rows < n_rows_ || (!use_loaded && src_pitch < row_bytes))
     return fail(EPS_USER_ERROR, "set_filter_program: attribute rows missing or shorter than the table");
   // validate: known opcodes, attribute loads inside a row, stack discipline
-  int sp = 0, maxsp = 0;
   bool uses_dist = false;
-  for (int i = 0; i < nops; ++i) {
-    const int op = ops[i].op;
-    if (op < EPS_FOP_PUSH_CONST || op > EPS_FOP_NE_BOOL) return fail(EPS_USER_ERROR, "set_filter_program: unknown opcode");
-    if (op <= EPS_FOP_PUSH_BOOL) {
-      static const int width[] = {0, 0, 0, 1, 2, 4, 8, 4, 8, 1};
-      if (op >= EPS_FOP_PUSH_I8 && (ops[i].arg < 0 || (int64_t)ops[i].arg + width[op] > stride))   // (in 64 bits: arg = INT32_MAX must not wrap)
-        return fail(EPS_USER_ERROR, "set_filter_program: attribute offset outside the row");
-      uses_dist |= op == EPS_FOP_PUSH_DIST;
-      ++sp;
-    } else if (op == EPS_FOP_NOT) {
-      if (sp < 1) return fail(EPS_USER_ERROR, "set_filter_program: stack underflow");
-    } else {
-      if (sp < 2) return fail(EPS_USER_ERROR, "set_filter_program: stack underflow");
-      --sp;
-    }
-    maxsp = std::max(maxsp, sp);
-  }
-  if (sp != 1 || maxsp > 16) return fail(EPS_USER_ERROR, "set_filter_program: the program must leave exactly one value (stack depth <= 16)");
+  const char* why;
+  if (filter_program_check(ops, nops, stride, &uses_dist, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("set_filter_program: ") + why);   // (filters_host.hpp)
   HIP_TRY(hipStreamSynchronize(stream_));
   if (!prog_buf_.reserve((size_t)nops * sizeof(FilterOp))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "set_filter_program: out of device memory");
   static_assert(sizeof(FilterOp) == sizeof(eps_filter_op), "FilterOp mirrors eps_filter_op");

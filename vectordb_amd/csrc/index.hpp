@@ -212,6 +212,14 @@ class Index : public IndexBase {
   int32_t search_diverse(const float* queries, int64_t nq, int32_t k, int32_t fetch_k, float lambda, const int64_t* cand_ids, const int64_t* cand_offsets,
                          int64_t n_cand, const eps_search_params* p, int64_t* ids_out, float* dist_out, float* score_out, int32_t* counts_out) override;
 
+  // a batch whose queries name one of n_progs filter programs each: the k closest rows visible under the standing state AND the query's program
+  // (eps_index_search_filters; filters.hip, plan: filters_host.hpp)
+  int32_t search_filters(const float* queries, int64_t nq, int32_t k, const eps_search_params* p, const eps_filter_op* ops, const int32_t* prog_offsets,
+                         int32_t n_progs, const int32_t* query_prog, const void* rows, int64_t stride_bytes, int64_t n_rows, int32_t flags, int32_t engine,
+                         int64_t* ids_out, float* dist_out, int32_t* counts_out, int64_t* visible_out);
+  // the last such call: per program its engine (0: it had no query) and its visible rows, the first min(cap, n_progs) of them; *n_progs_out = n_progs
+  int32_t filters_info(int32_t* engines_out, int64_t* visible_out, int32_t cap, int32_t* n_progs_out);
+
   int64_t row_count() const override { return n_rows_; }
 
   // ---- used by the engine translation units
@@ -285,6 +293,16 @@ class Index : public IndexBase {
                      int64_t longest, bool call_syncs, unsigned long long** d_evals_out);
   // search_diverse(): the selected rows' keys [nq][k] (its pool is run_buf_, its pair counter among_in_'s)
   DevBuf div_sel_;
+  // search_filters(): the call's own device copy of host attribute rows (the installed program's copy is used where it is the same table; never
+  // written); [instructions | order]; [block_of | blocks | items]; planes; [block counts | offsets]; lists; partial lists; a plane-engine
+  // program's queries and keys.  h_flt_: the planes' totals, written by the scan.  flt_last_*: what filters_info reports
+  DevBuf flt_rows_buf_, flt_in_, flt_work_, flt_planes_, flt_scan_, flt_lists_, flt_partial_, flt_q_, flt_keys_;
+  HostBuf h_flt_;
+  const void* flt_rows_host_ = nullptr;
+  int64_t flt_rows_stride_ = 0, flt_rows_uploaded_ = 0, flt_rows_version_ = -1;
+  std::vector<int32_t> flt_last_engine_;
+  std::vector<int64_t> flt_last_visible_;
+  int32_t filters_stage_rows(const void* rows, int64_t stride, int64_t n_rows, int32_t flags, const uint8_t** d_rows, int64_t* d_stride);
   // search_among(), search_group_rows(): the pairs given a distance are counted on the device.  h_evals_: the counter's page-locked copy - the
   // call's dist_evals, read by last_stats once the call's last event has passed (evals_pending_), so that a call with device results stays
   // asynchronous

@@ -571,6 +571,275 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   return EPS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ search_filters
+// The attribute rows the call's programs read, on the device: a device table in place, the rows load_table kept (rows null), the installed
+// program's cached copy where it mirrors the same host table under the append-only promise, else a copy of the call's own with the same
+// append-only rule.  Nothing the installed program reads is written.
+int32_t Index::filters_stage_rows(const void* rows, int64_t stride, int64_t n_rows, int32_t flags, const uint8_t** d_rows, int64_t* d_stride) {
+  *d_stride = stride;
+  if (!rows) {
+    *d_rows = prog_rows_buf_.as<uint8_t>();
+    *d_stride = loaded_attr_stride_;
+    return EPS_OK;
+  }
+  if (is_device_ptr(rows)) {
+    *d_rows = static_cast<const uint8_t*>(rows);
+    return EPS_OK;
+  }
+  const bool append_only = (flags & EPS_FILTER_ROWS_APPEND_ONLY) != 0;
+  if (append_only && prog_rows_host_ == rows && prog_rows_stride_ == stride && prog_rows_pitch_ == stride && prog_rows_uploaded_ >= n_rows && prog_rows_buf_.p) {
+    *d_rows = prog_rows_buf_.as<uint8_t>();
+    return EPS_OK;
+  }
+  const bool same = append_only && flt_rows_host_ == rows && flt_rows_stride_ == stride && flt_rows_version_ == rows_version_ && flt_rows_uploaded_ <= n_rows &&
+                    flt_rows_buf_.p;
+  const int64_t have_rows = same ? flt_rows_uploaded_ : 0;
+  const size_t bytes = (size_t)n_rows * (size_t)stride, have = (size_t)have_rows * (size_t)stride;
+  flt_rows_host_ = nullptr;   // (forgotten where the call fails below)
+  if (bytes > flt_rows_buf_.cap) {
+    const hipError_t e = flt_rows_buf_.grow_keeping(bytes + bytes / 2 + 16, have, stream_);
+    if (e == hipErrorOutOfMemory) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (attribute rows)");
+    if (e != hipSuccess) return hip_fail(e, "search_filters: moving the attribute rows");
+  }
+  if (n_rows > have_rows) HIP_TRY(hipMemcpyAsync(static_cast<char*>(flt_rows_buf_.p) + have, static_cast<const char*>(rows) + have, bytes - have, hipMemcpyHostToDevice, stream_));
+  HIP_TRY(hipStreamSynchronize(stream_));   // the host rows may change right after the call returns
+  flt_rows_host_ = rows;
+  flt_rows_stride_ = stride;
+  flt_rows_uploaded_ = n_rows;
+  flt_rows_version_ = rows_version_;
+  *d_rows = flt_rows_buf_.as<uint8_t>();
+  return EPS_OK;
+}
+
+int32_t Index::filters_info(int32_t* engines_out, int64_t* visible_out, int32_t cap, int32_t* n_progs_out) {
+  const int32_t np = (int32_t)flt_last_engine_.size();
+  for (int32_t j = 0; j < np && j < cap; ++j) {
+    if (engines_out) engines_out[j] = flt_last_engine_[(size_t)j];
+    if (visible_out) visible_out[j] = flt_last_visible_[(size_t)j];
+  }
+  if (n_progs_out) *n_progs_out = np;
+  return EPS_OK;
+}
+
+// Every query under its own program (filters.hip): one pass over the attribute rows judges all programs into verdict planes, ONE host sync reads
+// the planes' visible counts, then per plane the list engine (scatter, gather over the item table, merge) or the plane engine (the flat search
+// of that plane's queries with the plane as the deleted bitset).  Reports like a search (statistics, kernel ring); changes nothing a later call
+// can observe: the plane engine lends the flat engines the plane for the length of its launches and puts the standing state back.
+int32_t Index::search_filters(const float* queries, int64_t nq, int32_t k, const eps_search_params* pp, const eps_filter_op* ops, const int32_t* prog_offsets,
+                              int32_t n_progs, const int32_t* query_prog, const void* rows, int64_t stride_bytes, int64_t n_rows, int32_t flags, int32_t engine,
+                              int64_t* ids, float* dist, int32_t* counts, int64_t* visible) {
+  const eps_search_params p = search_params_or_default(pp);
+  if (k < 1 || k > FILTERS_MAX_K) return fail(EPS_USER_ERROR, "search_filters: k must be in [1, 1024]");
+  if (nq < 0) return fail(EPS_USER_ERROR, "search_filters: nq must be >= 0");
+  if (engine < EPS_FILTERS_AUTO || engine > EPS_FILTERS_PLANES) return fail(EPS_USER_ERROR, "search_filters: unknown engine");
+  if (!flat_engine_known(p.flat_engine)) return fail(EPS_USER_ERROR, "search_filters: unknown flat engine");
+  HIP_TRY(hipSetDevice(device_));
+  if ((ops && is_device_ptr(ops)) || (prog_offsets && is_device_ptr(prog_offsets)) || (query_prog && is_device_ptr(query_prog)))
+    return fail(EPS_USER_ERROR, "search_filters: ops, prog_offsets and query_prog must be host arrays");
+  const bool loaded = !rows && loaded_attr_rows_ > 0 && loaded_attr_rows_ >= n_rows_;   // the rows eps_index_load_table kept
+  const char* why;
+  int32_t rc = filters_programs_check(ops, prog_offsets, n_progs, rows ? stride_bytes : (loaded ? loaded_attr_stride_ : 0), &why);
+  if (rc != EPS_OK) return fail(rc, std::string("search_filters: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (!queries || !ids || !dist || !query_prog) return fail(EPS_USER_ERROR, "search_filters: null buffer");
+  if (prog_len_ > 0 && prog_uses_dist_)
+    return fail(EPS_USER_ERROR, "search_filters: the installed filter program reads @distance: a verdict plane is computed before any distance exists");
+  if (rows && n_rows != n_rows_)
+    return fail(EPS_USER_ERROR, "search_filters: n_rows must equal the table's row count (rows were appended: hand over the attribute rows of all of them)");
+  FiltersPlan plan;
+  if (filters_plan_queries(ops, prog_offsets, n_progs, query_prog, nq, &plan, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_filters: ") + why);
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_vis = rb.add(visible, (size_t)nq);
+  const auto r_dist = rb.add(dist, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr))
+    return fail(EPS_USER_ERROR, "search_filters: ids_out, dist_out, counts_out and visible_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
+  rc = check_filters_cover_table("search_filters");
+  if (rc != EPS_OK) return rc;
+  begin_timed_call();
+  prefilter_call_ = false;
+
+  const int64_t n = n_rows_;
+  const int32_t D = plan.planes;
+  const uint8_t* d_attr = nullptr;
+  int64_t d_stride = 0;
+  if (plan.op_off[(size_t)D] > 0) {
+    rc = filters_stage_rows(rows, stride_bytes, n_rows, flags, &d_attr, &d_stride);
+    if (rc != EPS_OK) return rc;
+  }
+  const float* dq;
+  rc = stage_queries("search_filters", queries, nq, &dq, true);   // (the sync below)
+  if (rc != EPS_OK) return rc;
+  if (!rb.place(out_block_) || !run_buf_.reserve((size_t)nq * k * sizeof(u64)))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (results)");
+  u64* run_keys = run_buf_.as<u64>();
+
+  // ---- the planes and their counts
+  std::vector<int64_t> count((size_t)D, 0);
+  const int64_t nblocks = select_blocks(n), plane_words = nblocks * (SEL_ROWS / 64);
+  const size_t ops_bytes = ((size_t)plan.op_off[(size_t)D] * sizeof(FilterOp) + 15) & ~(size_t)15;
+  if (!flt_in_.reserve(ops_bytes + (size_t)nq * 4 + 16)) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (scratch)");
+  int32_t* d_order = reinterpret_cast<int32_t*>(flt_in_.as<char>() + ops_bytes);
+  rc = copy_host_in(d_order, plan.order.data(), (size_t)nq * 4, true);
+  if (rc != EPS_OK) return rc;
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+  if (n > 0) {
+    static_assert(sizeof(FilterOp) == sizeof(eps_filter_op), "FilterOp mirrors eps_filter_op");
+    std::vector<eps_filter_op> plane_ops;
+    for (int32_t d = 0; d < D; ++d) {
+      const int32_t o = plan.prog_of_plane[(size_t)d];
+      plane_ops.insert(plane_ops.end(), ops + prog_offsets[o], ops + prog_offsets[o + 1]);
+    }
+    const size_t cnt_bytes = ((size_t)D * nblocks * sizeof(u32) + 15) & ~(size_t)15;
+    if (!flt_planes_.reserve((size_t)D * plane_words * sizeof(u64)) || !flt_scan_.reserve(cnt_bytes + (size_t)D * (nblocks + 1) * sizeof(u32)))
+      return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (verdict planes)");
+    if (!h_flt_.reserve(FILTERS_MAX_PROGS * sizeof(u32))) return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of page-locked host memory");
+    if (!plane_ops.empty()) {
+      rc = copy_host_in(flt_in_.p, plane_ops.data(), plane_ops.size() * sizeof(eps_filter_op), true);
+      if (rc != EPS_OK) return rc;
+    }
+    FiltersVerdictArgs v;
+    v.f = filter_spec();
+    v.f.prog_use_dist = 0;
+    v.ops = flt_in_.as<FilterOp>();
+    v.rows = d_attr;
+    v.stride = d_stride;
+    v.n = n;
+    v.planes_n = D;
+    v.p0 = v.p1 = 0;
+    for (int32_t d = 0; d <= FILTERS_MAX_PROGS; ++d) v.off[d] = plan.op_off[(size_t)std::min(d, D)];
+    v.planes = flt_planes_.as<u64>();
+    v.plane_words = plane_words;
+    v.counts = flt_scan_.as<u32>();
+    v.nblocks = nblocks;
+    u32* d_offsets = reinterpret_cast<u32*>(flt_scan_.as<char>() + cnt_bytes);
+    launch_filters_planes(v, plan.pass_begin.data(), (int)plan.pass_begin.size() - 1, d_offsets, static_cast<u32*>(h_flt_.p), stream_);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream_));   // the call's one sync in front of its main launch
+    for (int32_t d = 0; d < D; ++d) count[(size_t)d] = (int64_t) static_cast<const u32*>(h_flt_.p)[d];
+
+    // ---- the engines
+    const int block_q = pick_nq(FILTERS_BLOCK_Q, k, (int)dim_);
+    bool matrix[FILTERS_MAX_PROGS];
+    int64_t most_plane_queries = 0;
+    for (int32_t d = 0; d < D; ++d) {
+      const int64_t m = plan.plane_q0[(size_t)d + 1] - plan.plane_q0[(size_t)d];
+      matrix[d] = m > 0 && engine == EPS_FILTERS_AUTO && resolve_flat_engine(p.flat_engine, m, k, false).matrix;
+    }
+    filters_plan_engines(&plan, count.data(), n, k, block_q, engine, matrix, FILTERS_SCRATCH_BYTES);
+    if (plan.partial_waves > (int64_t)0x7fffffff / FILTERS_BLOCK_Q || plan.list_total > (int64_t)0x7fffffff)
+      return fail(EPS_DB_UNSUPPORTED_ERROR, "search_filters: the list engine's work does not fit 32-bit indices: use the plane engine");
+    for (int32_t d = 0; d < D; ++d)
+      if (plan.engine[(size_t)d] == EPS_FILTERS_PLANES) most_plane_queries = std::max<int64_t>(most_plane_queries, plan.plane_q0[(size_t)d + 1] - plan.plane_q0[(size_t)d]);
+
+    // the plane engine: the flat search of a plane's queries, the plane in the deleted bitset's place (it holds the standing verdict already)
+    if (most_plane_queries > 0) {
+      if (!flt_q_.reserve((size_t)most_plane_queries * dim_ * sizeof(float)) || !flt_keys_.reserve((size_t)most_plane_queries * k * sizeof(u64)))
+        return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (plane engine)");
+      struct Standing {   // put back on every way out
+        Index& ix;
+        const uint8_t* deleted;
+        int64_t deleted_bytes;
+        int32_t f_op, prog_len;
+        ~Standing() {
+          ix.d_deleted_ = deleted;
+          ix.deleted_bytes_ = deleted_bytes;
+          ix.f_op_ = f_op;
+          ix.prog_len_ = prog_len;
+        }
+      } standing{*this, d_deleted_, deleted_bytes_, f_op_, prog_len_};
+      for (int32_t d = 0; d < D; ++d) {
+        if (plan.engine[(size_t)d] != EPS_FILTERS_PLANES) continue;
+        const int64_t s0 = plan.plane_q0[(size_t)d], m = plan.plane_q0[(size_t)d + 1] - s0;
+        launch_range_gather(dq, (int)dim_, d_order + s0, m, flt_q_.as<float>(), nullptr, false, stream_);
+        d_deleted_ = reinterpret_cast<const uint8_t*>(flt_planes_.as<u64>() + (int64_t)d * plane_words);
+        deleted_bytes_ = plane_words * 8;
+        f_op_ = 0;
+        prog_len_ = 0;
+        const FlatChoice fc = resolve_flat_engine(p.flat_engine, m, k, false);
+        rc = fc.matrix ? flat_mfma_search(*this, flt_q_.as<float>(), m, k, flt_keys_.as<u64>(), false, fc.bits)
+                       : flat_stream_page(flt_q_.as<float>(), m, k, 0, n, flt_keys_.as<u64>(), -1, true, nullptr, 0);
+        if (rc != EPS_OK) return rc;
+        launch_groups_scatter(flt_keys_.as<u64>(), k, d_order + s0, m, run_keys, stream_);
+      }
+    }
+
+    // the list engine
+    if (plan.list_queries > 0) {
+      const size_t bo_bytes = ((size_t)nq * 4 + 15) & ~(size_t)15, blk_bytes = plan.blocks.size() * sizeof(FiltersBlock);
+      const size_t item_bytes = plan.items.size() * sizeof(FiltersItem);
+      if (!flt_work_.reserve(bo_bytes + blk_bytes + item_bytes + 16) || !flt_lists_.reserve((size_t)plan.list_total * sizeof(u32) + 16) ||
+          !flt_partial_.reserve((size_t)plan.partial_waves * block_q * k * sizeof(u64) + 16))
+        return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_filters: out of device memory (lists)");
+      FiltersGatherArgs g;
+      g.rows = d_rows_;
+      g.dim = (int)dim_;
+      g.metric = metric_;
+      g.queries = dq;
+      g.order = d_order;
+      g.k = k;
+      g.block_q = block_q;
+      g.block_of = flt_work_.as<int32_t>();
+      g.blocks = reinterpret_cast<const FiltersBlock*>(flt_work_.as<char>() + bo_bytes);
+      g.items = reinterpret_cast<const FiltersItem*>(flt_work_.as<char>() + bo_bytes + blk_bytes);
+      g.n_items = (int64_t)plan.items.size();
+      g.lists = flt_lists_.as<u32>();
+      g.partial = flt_partial_.as<u64>();
+      rc = copy_host_in(flt_work_.p, plan.block_of.data(), (size_t)nq * 4, !out_dev);
+      if (rc == EPS_OK) rc = copy_host_in(const_cast<FiltersBlock*>(g.blocks), plan.blocks.data(), blk_bytes, !out_dev);
+      if (rc == EPS_OK && item_bytes) rc = copy_host_in(const_cast<FiltersItem*>(g.items), plan.items.data(), item_bytes, !out_dev);
+      if (rc != EPS_OK) return rc;
+      FiltersScatterArgs sc;
+      sc.planes = flt_planes_.as<u64>();
+      sc.plane_words = plane_words;
+      sc.offsets = d_offsets;
+      sc.nblocks = nblocks;
+      sc.lists = flt_lists_.as<u32>();
+      sc.n_lists = 0;
+      for (int32_t d = 0; d < D; ++d)
+        if (plan.engine[(size_t)d] == EPS_FILTERS_LISTS && count[(size_t)d] > 0) {
+          sc.plane[sc.n_lists] = d;
+          sc.begin[sc.n_lists++] = plan.list_begin[(size_t)d];
+        }
+      launch_filters_scatter(sc, stream_);
+      HIP_TRY(hipEventRecord(evk0_, stream_));
+      launch_filters_gather(g, stream_);
+      HIP_TRY(hipEventRecord(evk1_, stream_));
+      launch_filters_merge(g, nq, run_keys, stream_);
+      set_main_kernel(1, plan.list_total, plan.list_queries, 32);
+      stats_.dist_evals += plan.list_evals;
+    }
+  } else {
+    launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);   // an empty table: nothing to judge
+    plan.engine.assign((size_t)D, 0);
+    HIP_TRY(hipStreamSynchronize(stream_));   // (the host arrays have been read when the call returns)
+  }
+
+  launch_finalize(run_keys, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_dist), rb.dev(r_cnt), stream_);
+  if (rb.dev(r_vis)) {
+    std::vector<int64_t> vis((size_t)nq);
+    for (int64_t q = 0; q < nq; ++q) vis[(size_t)q] = count[(size_t)plan.plane_of_prog[(size_t)query_prog[q]]];
+    rc = copy_host_in(rb.dev(r_vis), vis.data(), (size_t)nq * sizeof(int64_t), !out_dev);
+    if (rc != EPS_OK) return rc;
+  }
+  flt_last_engine_.assign((size_t)n_progs, 0);
+  flt_last_visible_.assign((size_t)n_progs, 0);
+  for (int32_t j = 0; j < n_progs; ++j) {
+    flt_last_engine_[(size_t)j] = plan.engine[(size_t)plan.plane_of_prog[(size_t)j]];
+    flt_last_visible_[(size_t)j] = count[(size_t)plan.plane_of_prog[(size_t)j]];
+  }
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(rb);
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ search_diverse
 // k rows of every query's pool by maximal marginal relevance (diverse.hip, layout: diverse_host.hpp).  The pool - fetch_k keys per query in
 // run_buf_ - is one page of the flat engine a search of (nq, fetch_k) would take, or search_among's gather and merge over the caller's lists; then

@@ -7,6 +7,7 @@
 #include "among_host.hpp"
 #include "device_common.hpp"
 #include "diverse_host.hpp"
+#include "filters_host.hpp"
 #include "group_rows_host.hpp"
 #include "groups_host.hpp"
 #include "merge_host.hpp"
@@ -207,6 +208,52 @@ struct AmongArgs {
 // the gather (in slices of AMONG_GRID_Y query tiles), then the merge of every query's partial lists into run_keys[nq][k]: sorted, unique
 void launch_among_gather(const AmongArgs& a, hipStream_t s);
 void launch_among_merge(const u64* partial, int W, int k, int64_t nq, u64* run_keys, hipStream_t s);
+
+// ---------------------------------------------------------------- search under per-query filters (eps_index_search_filters; filters.hip, plan: filters_host.hpp)
+struct FiltersVerdictArgs {
+  FilterSpec f;                 // the standing state (prog_use_dist = 0)
+  const FilterOp* ops;          // the planes' instructions, one program after the other
+  const uint8_t* rows;          // the packed attribute rows the programs read
+  int64_t stride;
+  int64_t n;                    // rows [0, n) are judged, 0 < n < 2^31
+  int32_t planes_n;             // distinct programs
+  int32_t p0, p1;               // the planes of one pass (set by the launcher)
+  int32_t off[FILTERS_MAX_PROGS + 1];   // where plane p's instructions start in ops
+  u64* planes;                  // [planes_n][plane_words] bit set = hidden, whole blocks of SEL_ROWS rows
+  int64_t plane_words;          // select_blocks(n) * SEL_ROWS / 64
+  u32* counts;                  // [planes_n][nblocks] visible rows per block
+  int64_t nblocks;              // select_blocks(n)
+};
+// the verdict passes, then the scan: offsets [planes_n][nblocks + 1], totals [planes_n] (host-mapped words)
+void launch_filters_planes(const FiltersVerdictArgs& a, const int32_t* pass_begin, int passes, u32* offsets, u32* totals, hipStream_t s);
+struct FiltersScatterArgs {
+  const u64* planes;
+  int64_t plane_words;
+  const u32* offsets;
+  int64_t nblocks;
+  u32* lists;                   // every list-engine plane's visible rows, plane after plane
+  int32_t n_lists;
+  int32_t plane[FILTERS_MAX_PROGS];   // [n_lists] which planes
+  int64_t begin[FILTERS_MAX_PROGS];   // [n_lists] where their lists start
+};
+void launch_filters_scatter(const FiltersScatterArgs& a, hipStream_t s);
+struct FiltersGatherArgs {
+  const float* rows;
+  int dim, metric;
+  const float* queries;         // [nq][dim] in the caller's order
+  const int32_t* order;         // [nq] sorted position -> the caller's query
+  int k;
+  int block_q;                  // queries a workgroup stages: the plan's
+  const FiltersBlock* blocks;
+  const FiltersItem* items;
+  int64_t n_items;
+  const int32_t* block_of;      // [nq] by sorted position: the query's block, -1: not on the list engine
+  const u32* lists;
+  u64* partial;                 // [the plan's partial_waves][block_q][k]
+};
+void launch_filters_gather(const FiltersGatherArgs& a, hipStream_t s);
+// run_keys[the caller's query][k] of every query on the list engine: sorted, unique
+void launch_filters_merge(const FiltersGatherArgs& a, int64_t nq, u64* run_keys, hipStream_t s);
 
 // ---------------------------------------------------------------- grouped search (eps_index_search_groups; groups.hip, plan: groups_host.hpp)
 constexpr u32 GROUPS_UNFINISHED = 1;   // a query's status while it holds fewer than k representatives and its last page was full

@@ -155,13 +155,7 @@ class GpuIndex:
         if not program:
             self._check(self.L.eps_index_set_filter_program(self.h, None, 0, None, 0, 0))
             return
-        ops = (lib.FilterOp * len(program))()
-        for i, ins in enumerate(program):
-            ops[i].op = lib.FOP[ins[0]]
-            if ins[0] == "const":
-                ops[i].dval = float(ins[1])
-            elif len(ins) > 1:
-                ops[i].arg = int(ins[1])
+        ops = _filter_ops(program)
         if rows is None:   # the attribute rows eps_index_load_table kept on the device
             self._check(self.L.eps_index_set_filter_program(self.h, ops, len(program), None, 0, 0))
             return
@@ -446,6 +440,47 @@ class GpuIndex:
                                                   _ptr(dist), _ptr(counts)))
         return out_ids, dist, counts
 
+    def search_filters(self, queries, k, programs, query_prog, rows=None, stride=None, append_only=False, engine="auto", flat_engine="auto", out=None):
+        """eps_index_search_filters: a batch in which query j is filtered by programs[query_prog[j]] - each a postfix list as set_filter_program
+        takes it ([] passes every row; no ("dist",)), at most 64 of them - on top of the index's standing bitset / column test / installed program.
+        rows, stride, append_only: the packed attribute rows as set_filter_program takes them (None: the rows load_table kept; len(rows) must be
+        the table's row count).  Returns (ids int64[nq, k], dist float32[nq, k], counts int32[nq], visible int64[nq]) in ascending (distance, id)
+        order, counts = min(k, visible), visible = the rows the query's filter leaves; the rest -1 / +inf.  The distances are a flat search's, bit
+        for bit.  engine: "auto" | "lists" | "planes" (or a FILTERS_* value), flat_engine as for search_range (what the plane engine runs): the same
+        bits from all of them.  NumPy queries give NumPy results; device queries give device tensors.  out=(ids, dist, counts, visible):
+        caller-provided buffers, all NumPy or all device.  filters_info() tells which engine served each program."""
+        k = int(k)
+        queries, nq = _queries_2d(queries, self.dim)
+        query_prog = np.ascontiguousarray(np.asarray(query_prog.cpu() if _is_dev(query_prog) else query_prog), np.int32).reshape(-1)
+        if query_prog.size != nq:
+            raise ValueError("search_filters: query_prog must hold nq = %d entries, got %d" % (nq, query_prog.size))
+        if not 1 <= len(programs) <= lib.FILTERS_MAX_PROGS:
+            raise ValueError("search_filters: between 1 and %d programs, got %d" % (lib.FILTERS_MAX_PROGS, len(programs)))
+        offsets = np.zeros(len(programs) + 1, np.int32)
+        np.cumsum([len(pr) for pr in programs], out=offsets[1:])
+        ops = _filter_ops([ins for pr in programs for ins in pr])
+        n_rows = 0
+        if rows is not None:
+            if not _is_dev(rows):
+                rows = np.ascontiguousarray(rows)
+                stride = stride or rows.strides[0]
+            n_rows = rows.shape[0]
+        ids, dist, counts, visible = _results("search_filters", (("ids", (nq, k), "int64"), ("dist", (nq, k), "float32"), ("counts", (nq,), "int32"),
+                                                                 ("visible", (nq,), "int64")), out, queries)
+        p = self.params(flat_engine=RANGE_ENGINES[flat_engine])
+        self._keep["filters"] = (queries, rows)   # (device results: the call is still running when this returns)
+        self._check(self.L.eps_index_search_filters(self.h, _ptr(queries), nq, k, C.byref(p), ops, _ptr(offsets), len(programs), _ptr(query_prog), _ptr(rows),
+                                                    int(stride or 0), n_rows, lib.FILTER_ROWS_APPEND_ONLY if append_only else 0, FILTERS_ENGINES[engine],
+                                                    _ptr(ids), _ptr(dist), _ptr(counts), _ptr(visible)))
+        return ids, dist, counts, visible
+
+    def filters_info(self):
+        """eps_index_filters_info: (engines int32[n_progs], visible int64[n_progs]) of the last search_filters - per program FILTERS_LISTS,
+        FILTERS_PLANES or 0 (it had no query), and the rows it leaves visible"""
+        engines, visible, n = np.zeros(lib.FILTERS_MAX_PROGS, np.int32), np.zeros(lib.FILTERS_MAX_PROGS, np.int64), C.c_int32(0)
+        self._check(self.L.eps_index_filters_info(self.h, _ptr(engines), _ptr(visible), lib.FILTERS_MAX_PROGS, C.byref(n)))
+        return engines[:n.value], visible[:n.value]
+
     def search_diverse(self, queries, k, fetch_k, lam=0.5, ids=None, offsets=None, flat_engine="auto", out=None):
         """eps_index_search_diverse: per query k rows of its pool by greedy maximal marginal relevance - step 1 takes the closest row, every later
         step the unselected row with the smallest lam * d(row, query) - (1 - lam) * min over the selected rows s of D(row, s), ties to the earlier pool
@@ -668,6 +703,24 @@ RANGE_ENGINES = {"auto": FLAT_AUTO, "stream": FLAT_STREAM, "mfma": FLAT_MFMA, "m
 
 GROUPS_AUTO, GROUPS_PAGES, GROUPS_SCAN = 0, 1, 2
 GROUPS_ENGINES = {"auto": GROUPS_AUTO, "pages": GROUPS_PAGES, "scan": GROUPS_SCAN, GROUPS_AUTO: GROUPS_AUTO, GROUPS_PAGES: GROUPS_PAGES, GROUPS_SCAN: GROUPS_SCAN}
+
+
+FILTERS_ENGINES = {"auto": lib.FILTERS_AUTO, "lists": lib.FILTERS_LISTS, "planes": lib.FILTERS_PLANES, lib.FILTERS_AUTO: lib.FILTERS_AUTO,
+                   lib.FILTERS_LISTS: lib.FILTERS_LISTS, lib.FILTERS_PLANES: lib.FILTERS_PLANES}
+
+
+def _filter_ops(program):
+    """a postfix list (GpuIndex.set_filter_program) as an array of eps_filter_op; None where it is empty"""
+    if not program:
+        return None
+    ops = (lib.FilterOp * len(program))()
+    for i, ins in enumerate(program):
+        ops[i].op = lib.FOP[ins[0]]
+        if ins[0] == "const":
+            ops[i].dval = float(ins[1])
+        elif len(ins) > 1:
+            ops[i].arg = int(ins[1])
+    return ops
 
 
 def _range_spec(nq, cap):
