@@ -39,6 +39,8 @@
  *   eps_sparse_index_*              BruteForceSearch over a SPARSE_VECTOR_FLOAT field: GetL2DistSqr / GetCosineDist / GetInnerProductDist
  *                                   (db/vector.cpp:7-96) row by row, as an exact scan of a CSR table; for dot and cosine also term at a
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
+ *   eps_index_search_hybrid         (new) the k rows with the smallest weighted sum of a dense and a sparse distance, over a dense handle and a
+ *                                   sparse handle that hold the same records, in one fused pass; the reference has no relative
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -733,6 +735,42 @@ int32_t eps_sparse_index_build_inverted(eps_sparse_index* h);
 int32_t eps_sparse_index_drop_inverted(eps_sparse_index* h);
 int32_t eps_sparse_index_inverted_info(const eps_sparse_index* h, int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine);
 int32_t eps_sparse_index_get_inverted(eps_sparse_index* h, int64_t* col_offsets, int32_t* rows, float* values);
+
+/* Hybrid search: for every query j the k rows with the smallest  w_dense * d_dense + w_sparse * d_sparse  - an embedding next to a BM25 /
+ * SPLADE-style sparse vector.  The first call that joins the two handle kinds.  Before, the exact route was every row's distance from both handles
+ * added on the host; fusing two top-k lists is not exact - a row that is 11th in both lists can be 1st in the sum, and neither list holds it.
+ * Rows.  Row r of h and row r of s are the same record: eps_index_row_count(h) != eps_sparse_index_row_count(s), or handles on different devices:
+ * EPS_USER_ERROR.
+ * Terms.  d_dense(r, j) is, bit for bit, what eps_index_search in EPS_MODE_FLAT returns for (row r, queries[j]) under h's metric; d_sparse(r, j)
+ * is, bit for bit, what eps_sparse_index_search returns for (row r, sparse query j) under s's metric - an empty side under COSINE gives NaN.
+ * queries: host or device float[nq][dim of h]; q_offsets / q_indices / q_values: nq sparse queries as eps_sparse_index_search reads them (q_offsets
+ * a HOST int64[nq + 1]; indices and values both host - validated on the host, copied on h's stream - or both device - validated by one small
+ * launch whose verdict the call reads back).
+ * Score.  score = (w_dense * d_dense) + (w_sparse * d_sparse): each multiply rounded to fp32, then one rounded add, nothing contracted.  Scores
+ * order as distances do everywhere in the library: -0 equals +0, every NaN after +inf, ties to the smaller row; a NaN row is still a row.
+ * Visibility.  Row r is visible iff it is visible under h's standing state (deleted bitset, int-column test, installed program) and its bit in s's
+ * deleted bitset is clear.  An installed program that reads `@distance`: EPS_USER_ERROR - there is no single distance for it to read.
+ * Outputs, [nq][k] in ascending (score, id) order: ids_out through h's id map (s's id map is not read); score_out = the score as its key holds it
+ * (-0 as +0, a NaN as the quiet NaN); dense_out and sparse_out (either may be NULL) = the two terms of each returned row; counts_out [nq] (may be
+ * NULL) = min(k, visible); the unused slots -1 / +inf / +inf / +inf.  Host or device, all of one kind - device: on h's stream, the caller
+ * synchronises, and the call has no host sync of its own (but the verdict's, with device-resident sparse queries); host: the call synchronises.
+ * Host arrays are read before the call returns.  The call runs on h's stream; it first waits, by an event, for work queued on s's stream.
+ * Limits and refusals.  1 <= k <= 1024 and finite weights, else EPS_USER_ERROR.  s must be DOT_PRODUCT or COSINE and hold an inverted image
+ * (eps_sparse_index_build_inverted), else EPS_DB_UNSUPPORTED_ERROR naming what is missing.  A sparse query of more than 1024 non-zeros - its pairs
+ * are staged in LDS next to the dense queries - or a dim whose single query no longer fits there (above 12288 at 1024 non-zeros):
+ * EPS_DB_UNSUPPORTED_ERROR, before any launch.  A sharded h: EPS_DB_UNSUPPORTED_ERROR.  nq = 0: EPS_OK.  Malformed sparse queries, null required
+ * buffers, outputs of mixed kinds, stale filters after an append: the errors of eps_sparse_index_search and eps_index_search_among.
+ * One fused pass (csrc/hybrid.hip; plan and LDS layout: csrc/hybrid_host.hpp): a workgroup stages up to 4 dense queries and their sparse pairs in
+ * LDS, each wavefront walks its rows in tiles of 512 - the sparse queries' terms are summed term at a time into per-row LDS accumulators
+ * (sparse_inverted.hip's match and sum), the tile's dense rows run through the flat scan's arithmetic, and the first lane of each row group
+ * finishes both terms, forms the score and offers the key.  No [nq][n] table of sparse distances exists in HBM; traffic is n * dim * 4 bytes of
+ * rows per 4 queries plus the postings of the queries' terms.  A second small launch recomputes the two terms of the nq * k winners (skipped when
+ * dense_out and sparse_out are both NULL).
+ * eps_index_last_stats(h) reports the call like a search: dist_evals = n * nq, main_kernel_bits 32, main_kernel_rows = n, main_kernel_queries = nq,
+ * main_kernel_ms = the fused pass.  Nothing a later call on either handle can observe changes; s's statistics are not touched. */
+int32_t eps_index_search_hybrid(eps_index* h, eps_sparse_index* s, const float* queries, const int64_t* q_offsets, const int32_t* q_indices,
+                                const float* q_values, int64_t nq, int32_t k, float w_dense, float w_sparse, int64_t* ids_out, float* score_out,
+                                float* dense_out, float* sparse_out, int32_t* counts_out);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

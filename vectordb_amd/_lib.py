@@ -39,7 +39,7 @@ EXPORTS = [
     "eps_sparse_index_create", "eps_sparse_index_destroy", "eps_sparse_index_last_error", "eps_sparse_index_set_stream", "eps_sparse_index_synchronize",
     "eps_sparse_index_attach_csr", "eps_sparse_index_row_count", "eps_sparse_index_set_id_map", "eps_sparse_index_set_deleted", "eps_sparse_index_search",
     "eps_sparse_index_last_stats", "eps_sparse_index_build_inverted", "eps_sparse_index_drop_inverted", "eps_sparse_index_inverted_info",
-    "eps_sparse_index_get_inverted",
+    "eps_sparse_index_get_inverted", "eps_index_search_hybrid",
 ]
 
 # Engine-selection switches of the library (eps_set_tuning, include/epsilla_gfx950.h).  The library itself reads no environment
@@ -88,7 +88,7 @@ class _Synced:
     """The loaded library; calls that may consult a switch forward the environment first (see sync_tuning)."""
     _SYNC = frozenset(("eps_index_search", "eps_index_search_walk", "eps_index_build", "eps_index_knn_graph", "eps_index_link",
                        "eps_index_attach_rows", "eps_index_append_rows", "eps_index_set_graph", "eps_index_load_graph",
-                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse", "eps_index_search_filters"))
+                       "eps_index_mirror_view", "eps_index_filter_pass", "eps_index_one_pass_probe", "eps_index_search_range", "eps_index_search_among", "eps_index_search_groups", "eps_index_search_group_rows", "eps_index_search_multi", "eps_index_search_diverse", "eps_index_search_filters", "eps_index_search_hybrid"))
 
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
@@ -267,6 +267,7 @@ def load():
     L.eps_sparse_index_set_id_map.argtypes = [vp, i64, i64]
     L.eps_sparse_index_set_deleted.argtypes = [vp, vp, i64]
     L.eps_sparse_index_search.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    L.eps_index_search_hybrid.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp]
     L.eps_sparse_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     L.eps_sparse_index_build_inverted.argtypes = [vp]
     L.eps_sparse_index_drop_inverted.argtypes = [vp]

@@ -493,6 +493,16 @@ int32_t eps_sparse_index_get_inverted(eps_sparse_index* h, int64_t* col_offsets,
   return on_sparse(h, [&](eps::SparseIndex& ix) { return ix.get_inverted(col_offsets, rows, values); });
 }
 
+// ---- hybrid search: a dense handle and a sparse handle over the same records (Index::search_hybrid; kernels: hybrid.hip)
+int32_t eps_index_search_hybrid(eps_index* h, eps_sparse_index* s, const float* queries, const int64_t* q_offsets, const int32_t* q_indices,
+                                const float* q_values, int64_t nq, int32_t k, float w_dense, float w_sparse, int64_t* ids, float* score, float* dense,
+                                float* sparse, int32_t* counts) {
+  if (h && !s) return IX(h)->fail(EPS_USER_ERROR, "search_hybrid: the sparse handle is null");
+  return on_single_device(h, "search_hybrid: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER, [&](Index& ix) {
+    return ix.search_hybrid(SIX(s)->view(), queries, q_offsets, q_indices, q_values, nq, k, w_dense, w_sparse, ids, score, dense, sparse, counts);
+  });
+}
+
 int32_t eps_set_tuning(const char* name, const char* value) {
   eps::tune_set(name, value);
   return EPS_OK;

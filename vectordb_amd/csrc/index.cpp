@@ -158,6 +158,7 @@ Index::~Index() {
   if (mirror_) half_mirror_free(mirror_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
+  if (hyb_ev_) (void)hipEventDestroy(hyb_ev_);
   for (auto& pr : kring_)
     for (auto& e : pr)
       if (e) (void)hipEventDestroy(e);

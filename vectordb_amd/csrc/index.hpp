@@ -92,6 +92,21 @@ struct Quant8View {   // the table's 8-bit mirror as other kernels see it (mirro
 struct HalfMirror;   // fp16 + 8-bit mirrors and per-row bounds for the MFMA filter engine (mirror.hpp, built in mirror_build.hip)
 struct GraphDev;     // device CSR + traversal scratch (traverse.hip)
 
+// What a sparse-vector handle shows the hybrid search (Index::search_hybrid): its table, image and bitset as they stand, read-only - device
+// pointers that stay valid while the handle is not given another table, image or bitset.  SparseIndex::view fills it and changes nothing.
+struct SparseView {
+  const int64_t* offsets = nullptr;       // the validated CSR
+  const int32_t* indices = nullptr;
+  const float* values = nullptr;
+  const float* norms = nullptr;           // [n] the rows' sums of squares
+  const int64_t* col_offsets = nullptr;   // the inverted image, null without one
+  const SparsePosting* postings = nullptr;
+  const uint8_t* deleted = nullptr;       // null: no bitset
+  int64_t n = 0, dim = 0;
+  int metric = 0, device = 0;
+  hipStream_t stream = nullptr;
+};
+
 // What the C ABI dispatches to: one device index, or a group of them over a hash-sharded table (shard_group.cpp).
 class IndexBase {
  public:
@@ -220,6 +235,11 @@ class Index : public IndexBase {
   // the last such call: per program its engine (0: it had no query) and its visible rows, the first min(cap, n_progs) of them; *n_progs_out = n_progs
   int32_t filters_info(int32_t* engines_out, int64_t* visible_out, int32_t cap, int32_t* n_progs_out);
 
+  // the k rows with the smallest (w_dense * d_dense) + (w_sparse * d_sparse) over this table and the sparse table `sv` shows, row r of both the
+  // same record (eps_index_search_hybrid; hybrid.hip, plan: hybrid_host.hpp)
+  int32_t search_hybrid(const SparseView& sv, const float* queries, const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq,
+                        int32_t k, float w_dense, float w_sparse, int64_t* ids_out, float* score_out, float* dense_out, float* sparse_out, int32_t* counts_out);
+
   int64_t row_count() const override { return n_rows_; }
 
   // ---- used by the engine translation units
@@ -293,6 +313,10 @@ class Index : public IndexBase {
                      int64_t longest, bool call_syncs, unsigned long long** d_evals_out);
   // search_diverse(): the selected rows' keys [nq][k] (its pool is run_buf_, its pair counter among_in_'s)
   DevBuf div_sel_;
+  // search_hybrid(): [a device batch's verdict | the sparse queries' offsets | a host batch's indices | values]; the event by which the call waits
+  // for the sparse handle's stream (created at the first such call)
+  DevBuf hyb_in_;
+  hipEvent_t hyb_ev_ = nullptr;
   // search_filters(): the call's own device copy of host attribute rows (the installed program's copy is used where it is the same table; never
   // written); [instructions | order]; [block_of | blocks | items]; planes; [block counts | offsets]; lists; partial lists; a plane-engine
   // program's queries and keys.  h_flt_: the planes' totals, written by the scan.  flt_last_*: what filters_info reports
@@ -426,6 +450,7 @@ class SparseIndex {
   int32_t drop_inverted();
   int32_t inverted_info(int64_t* columns, int64_t* postings, int64_t* longest_column, int32_t* last_engine) const;
   int32_t get_inverted(int64_t* col_offsets, int32_t* rows, float* values);
+  SparseView view() const;   // for Index::search_hybrid: nothing of the handle changes
   const char* last_error() const { return err_.c_str(); }
   int32_t fail(int32_t code, const std::string& msg) {
     err_ = msg;

@@ -571,6 +571,167 @@ int32_t Index::search_among(const float* queries, int64_t nq, const int64_t* can
   return EPS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ search_hybrid
+// The k smallest (w_dense * d_dense) + (w_sparse * d_sparse) over the rows visible on both handles (hybrid.hip): the sparse queries onto this
+// index's own scratch, a wait for the sparse handle's stream, the fused pass, the merge of its lists, the result conversion and - where asked for -
+// the winners' two terms.  Nothing of the sparse handle is written: `sv` is a read-only view.  No host sync of its own with device results, except
+// the read of the verdict on device-resident sparse queries.  Reports like a search (statistics, kernel ring); changes nothing a later call on
+// either handle can observe.
+int32_t Index::search_hybrid(const SparseView& sv, const float* queries, const int64_t* q_offsets, const int32_t* q_indices, const float* q_values, int64_t nq,
+                             int32_t k, float w_dense, float w_sparse, int64_t* ids, float* score, float* dense, float* sparse, int32_t* counts) {
+  const char* why;
+  if (hybrid_args_check(nq, k, w_dense, w_sparse, &why) != EPS_OK) return fail(EPS_USER_ERROR, std::string("search_hybrid: ") + why);
+  if (nq == 0) return EPS_OK;
+  if (sv.n != n_rows_)
+    return fail(EPS_USER_ERROR, "search_hybrid: the handles hold " + std::to_string((long long)n_rows_) + " and " + std::to_string((long long)sv.n) +
+                                    " rows: row r of both must be the same record");
+  if (sv.device != device_) return fail(EPS_USER_ERROR, "search_hybrid: the two handles are on different devices");
+  if (sv.metric == EPS_METRIC_EUCLIDEAN)
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "search_hybrid: the sparse handle is EUCLIDEAN: a DOT_PRODUCT or COSINE handle is needed (L2 has no term-at-a-time form)");
+  if (!sv.col_offsets)
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "search_hybrid: the sparse handle has no inverted image: call eps_sparse_index_build_inverted first");
+  HIP_TRY(hipSetDevice(device_));
+  if (!queries || !q_offsets || !ids || !score) return fail(EPS_USER_ERROR, "search_hybrid: null buffer");
+  if (is_device_ptr(q_offsets)) return fail(EPS_USER_ERROR, "search_hybrid: q_offsets must be a host array");
+  int64_t qnnz = 0, longest = 0, bad = -1;
+  int32_t kind = 0;
+  if (sparse_offsets_check(q_offsets, nq, &qnnz, &longest, &bad, &kind) != EPS_OK)
+    return fail(EPS_USER_ERROR, "search_hybrid: query " + std::to_string((long long)bad) + ": " + sparse_bad_text(kind));
+  if (longest > HYB_MAX_QUERY_NNZ) {
+    int64_t j = 0;
+    while (q_offsets[j + 1] - q_offsets[j] <= HYB_MAX_QUERY_NNZ) ++j;
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "search_hybrid: sparse query " + std::to_string((long long)j) + " has " +
+                                              std::to_string((long long)(q_offsets[j + 1] - q_offsets[j])) + " non-zeros; at most " +
+                                              std::to_string((long long)HYB_MAX_QUERY_NNZ) + " per query are staged next to the dense queries");
+  }
+  bool q_dev = false;
+  if (qnnz > 0) {
+    if (!q_indices || !q_values) return fail(EPS_USER_ERROR, "search_hybrid: null buffer");
+    q_dev = is_device_ptr(q_indices);
+    if (is_device_ptr(q_values) != q_dev) return fail(EPS_USER_ERROR, "search_hybrid: q_indices and q_values must both be host or both be device arrays");
+  }
+  if (!q_dev && qnnz > 0 && sparse_rows_check(q_offsets, q_indices, nq, sv.dim, &bad, &kind) != EPS_OK)
+    return fail(EPS_USER_ERROR, "search_hybrid: query " + std::to_string((long long)bad) + ": " + sparse_bad_text(kind));
+  ResultBlock rb;
+  const auto r_ids = rb.add(ids, (size_t)nq * k);
+  const auto r_score = rb.add(score, (size_t)nq * k);
+  const auto r_dense = rb.add(dense, (size_t)nq * k);
+  const auto r_sparse = rb.add(sparse, (size_t)nq * k);
+  const auto r_cnt = rb.add(counts, (size_t)nq);
+  if (!rb.one_kind(is_device_ptr))
+    return fail(EPS_USER_ERROR, "search_hybrid: ids_out, score_out, dense_out, sparse_out and counts_out must all be host or all be device pointers");
+  const bool out_dev = rb.device();
+  if (prog_len_ > 0 && prog_uses_dist_)
+    return fail(EPS_USER_ERROR, "search_hybrid: the installed filter program reads @distance: a row has two distances here and no single one to read");
+  int32_t rc = check_filters_cover_table("search_hybrid");
+  if (rc != EPS_OK) return rc;
+  const int64_t n = n_rows_;
+  HybridPlan plan;
+  if (!hybrid_plan(n, nq, k, dim_, longest, &plan))
+    return fail(EPS_DB_UNSUPPORTED_ERROR, "search_hybrid: dim " + std::to_string((long long)dim_) + " with sparse queries of up to " +
+                                              std::to_string((long long)longest) + " non-zeros does not fit a workgroup's LDS (at most dim " +
+                                              std::to_string((long long)hybrid_max_dim(plan.rows.qcap)) + ")");
+  begin_timed_call();
+  prefilter_call_ = false;
+
+  const float* dq;
+  rc = stage_queries("search_hybrid", queries, nq, &dq, !out_dev);
+  if (rc != EPS_OK) return rc;
+
+  // ---- scratch: [verdict | q_offsets | a host batch's indices | values], partial lists, result keys, a host call's result block
+  const size_t off_bytes = (size_t)(nq + 1) * sizeof(int64_t), el_bytes = q_dev ? 0 : (size_t)qnnz * 4;
+  if (!hyb_in_.reserve(16 + off_bytes + 2 * el_bytes + 16) || !partial_buf_.reserve((size_t)nq * plan.rows.W * k * sizeof(u64)) ||
+      !run_buf_.reserve((size_t)nq * k * sizeof(u64)) || !rb.place(out_block_))
+    return fail(EPS_INFRA_UNEXPECTED_ERROR, "search_hybrid: out of device memory (scratch)");
+  int64_t* d_qoff = reinterpret_cast<int64_t*>(hyb_in_.as<char>() + 16);
+  const int32_t* d_qidx = q_indices;
+  const float* d_qval = q_values;
+  rc = copy_host_in(d_qoff, q_offsets, off_bytes, !out_dev);
+  if (rc != EPS_OK) return rc;
+  if (!q_dev && qnnz > 0) {
+    char* base = hyb_in_.as<char>() + 16 + off_bytes;
+    rc = copy_host_in(base, q_indices, el_bytes, !out_dev);
+    if (rc == EPS_OK) rc = copy_host_in(base + el_bytes, q_values, el_bytes, !out_dev);
+    if (rc != EPS_OK) return rc;
+    d_qidx = reinterpret_cast<const int32_t*>(base);
+    d_qval = reinterpret_cast<const float*>(base + el_bytes);
+  }
+  if (q_dev) {   // device-resident sparse queries: one small launch, and the read of its verdict, in front of the pass (as eps_sparse_index_search)
+    SparseVerdict v{~0ull, 0ull};
+    HIP_TRY(hipMemcpyAsync(hyb_in_.p, &v, sizeof(v), hipMemcpyHostToDevice, stream_));
+    SparseValidateArgs va;
+    va.offsets = d_qoff;
+    va.indices = d_qidx;
+    va.values = d_qval;
+    va.n = nq;
+    va.nnz = qnnz;
+    va.dim = sv.dim;
+    va.norms = nullptr;
+    va.verdict = hyb_in_.as<SparseVerdict>();
+    launch_sparse_validate(va, stream_);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&v, hyb_in_.p, sizeof(v), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (v.first_bad != ~0ull)
+      return fail(EPS_USER_ERROR, "search_hybrid: query " + std::to_string((long long)(v.first_bad >> 3)) + ": " + sparse_bad_text((int32_t)(v.first_bad & 7)));
+  }
+  if (sv.stream != stream_) {   // the sparse table, image and bitset may still be on their way on the other handle's stream
+    if (!hyb_ev_) HIP_TRY(hipEventCreateWithFlags(&hyb_ev_, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(hyb_ev_, sv.stream));
+    HIP_TRY(hipStreamWaitEvent(stream_, hyb_ev_, 0));
+  }
+  u64* run_keys = run_buf_.as<u64>();
+  HIP_TRY(hipEventRecord(ev0_, stream_));
+
+  HybridArgs a;
+  a.rows = d_rows_;
+  a.n = n;
+  a.dim = (int)dim_;
+  a.metric = metric_;
+  a.queries = dq;
+  a.sp_offsets = sv.offsets;
+  a.sp_indices = sv.indices;
+  a.sp_values = sv.values;
+  a.col_offsets = sv.col_offsets;
+  a.postings = sv.postings;
+  a.norms = sv.norms;
+  a.sp_metric = sv.metric;
+  a.sp_deleted = sv.deleted;
+  a.q_offsets = d_qoff;
+  a.q_indices = d_qidx;
+  a.q_values = d_qval;
+  a.nq = nq;
+  a.k = k;
+  a.w_dense = w_dense;
+  a.w_sparse = w_sparse;
+  a.f = filter_spec();
+  a.plan = plan;
+  a.partial = partial_buf_.as<u64>();
+  a.run_keys = run_keys;
+  a.dense_out = dense ? rb.dev(r_dense) : nullptr;
+  a.sparse_out = sparse ? rb.dev(r_sparse) : nullptr;
+  set_main_kernel(n > 0 ? (plan.rows.tiles + HYB_GRID_Y - 1) / HYB_GRID_Y : 0, n, nq, 32);
+  stats_.dist_evals = n * nq;
+  if (n > 0) {
+    HIP_TRY(hipEventRecord(evk0_, stream_));
+    launch_hybrid_tiles(a, stream_);
+    HIP_TRY(hipEventRecord(evk1_, stream_));
+    launch_among_merge(a.partial, plan.rows.W, k, nq, run_keys, stream_);
+  } else {
+    launch_fill_u64(run_keys, nq * k, KEY_EMPTY, stream_);
+  }
+  launch_finalize(run_keys, nq, k, id_base_, id_stride_, rb.dev(r_ids), rb.dev(r_score), rb.dev(r_cnt), stream_);
+  launch_hybrid_parts(a, stream_);
+  HIP_TRY(hipEventRecord(ev1_, stream_));
+  if (!out_dev) {
+    rc = fetch_to_host(rb);
+    if (rc != EPS_OK) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  end_timed_call();
+  return EPS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ search_filters
 // The attribute rows the call's programs read, on the device: a device table in place, the rows load_table kept (rows null), the installed
 // program's cached copy where it mirrors the same host table under the append-only promise, else a copy of the call's own with the same

@@ -10,6 +10,7 @@
 #include "filters_host.hpp"
 #include "group_rows_host.hpp"
 #include "groups_host.hpp"
+#include "hybrid_host.hpp"
 #include "merge_host.hpp"
 #include "multi_host.hpp"
 #include "sparse_host.hpp"
@@ -442,6 +443,38 @@ struct SparseInvArgs {
   u64* partial;                 // [nq][plan.rows.W][k] per-wavefront sorted lists
 };
 void launch_sparse_inverted(const SparseInvArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- hybrid search (eps_index_search_hybrid; hybrid.hip, plan: hybrid_host.hpp)
+struct HybridArgs {
+  const float* rows;            // the dense table [n][dim]
+  int64_t n;                    // rows of both tables, 0 < n < 2^31
+  int dim, metric;              // of the dense table
+  const float* queries;         // [nq][dim]
+  const int64_t* sp_offsets;    // the sparse table's CSR (hybrid_parts_kernel walks a winner's row)
+  const int32_t* sp_indices;
+  const float* sp_values;
+  const int64_t* col_offsets;   // ... and its image
+  const SparsePosting* postings;
+  const float* norms;           // [n] the sparse rows' sums of squares
+  int sp_metric;                // 1 COSINE, 2 DOT_PRODUCT
+  const uint8_t* sp_deleted;    // the sparse handle's bitset, or null
+  const int64_t* q_offsets;     // [nq + 1] the sparse queries, validated
+  const int32_t* q_indices;
+  const float* q_values;
+  int64_t nq;
+  int k;
+  float w_dense, w_sparse;
+  FilterSpec f;                 // the dense handle's standing state
+  HybridPlan plan;
+  u64* partial;                 // [nq][plan.rows.W][k] per-wavefront sorted lists
+  const u64* run_keys;          // [nq][k] the merged lists (hybrid_parts_kernel)
+  float* dense_out;             // [nq][k] or null
+  float* sparse_out;            // [nq][k] or null
+};
+// the fused pass (in slices of HYB_GRID_Y query tiles); launch_among_merge joins its lists
+void launch_hybrid_tiles(const HybridArgs& a, hipStream_t s);
+// the two terms of every key of a.run_keys, +inf where a slot is unused; nothing where both outputs are null
+void launch_hybrid_parts(const HybridArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch

@@ -387,6 +387,25 @@ int32_t SparseIndex::get_inverted(int64_t* col_offsets, int32_t* rows, float* va
   return EPS_OK;
 }
 
+SparseView SparseIndex::view() const {
+  SparseView v;
+  v.offsets = t_.offsets;
+  v.indices = t_.indices;
+  v.values = t_.values;
+  v.norms = t_.norms.as<float>();
+  if (inv_.built) {
+    v.col_offsets = inv_.col_offsets.as<int64_t>();
+    v.postings = inv_.postings.as<SparsePosting>();
+  }
+  v.deleted = d_deleted_;
+  v.n = t_.n;
+  v.dim = dim_;
+  v.metric = metric_;
+  v.device = device_;
+  v.stream = stream_;
+  return v;
+}
+
 int32_t SparseIndex::last_stats(eps_search_stats* out) {
   eps_search_stats s = stats_;
   if (ev0_ && s.main_kernel_queries > 0 && hipEventSynchronize(ev1_) == hipSuccess) {   // (read lazily: the caller may have left the work in flight)

@@ -517,6 +517,47 @@ class GpuIndex:
                                                     _ptr(out_ids), _ptr(dist), _ptr(score), _ptr(counts)))
         return out_ids, dist, score, counts
 
+    def search_hybrid(self, sparse_index, queries, sparse_queries, k, w_dense=1.0, w_sparse=1.0, parts=True, out=None):
+        """eps_index_search_hybrid: per query the k visible rows with the smallest (w_dense * d_dense) + (w_sparse * d_sparse) over this index and
+        sparse_index (a GpuSparseIndex with inverted lists, DOT_PRODUCT or COSINE, holding the same records row by row).  queries: [nq, dim];
+        sparse_queries: as GpuSparseIndex.search takes them - an (offsets, indices, values) triple, offsets on the host, or a list of dicts.  A row
+        is visible when this index's standing filters show it and sparse_index's deleted bitset does not hide it; ids go through this index's id
+        map.  Returns (ids int64[nq, k], score float32[nq, k], dense float32[nq, k], sparse float32[nq, k], counts int32[nq]) in ascending
+        (score, id) order, the rest -1 / +inf / +inf / +inf; dense and sparse are the two terms, with the bits search() and
+        GpuSparseIndex.search() return.  parts=False: the two terms are not computed (None in their places).  NumPy queries give NumPy results;
+        device queries give device tensors and the call is asynchronous on this index's stream.  out=(ids, score, dense, sparse, counts):
+        caller-provided buffers, all NumPy or all device (dense / sparse may be None)."""
+        from .sparse_index import _csr, _size, queries_from_dicts
+        k = int(k)
+        queries, nq = _queries_2d(queries, self.dim)
+        if isinstance(sparse_queries, list) and (not sparse_queries or isinstance(sparse_queries[0], dict)):
+            sparse_queries = queries_from_dicts(sparse_queries)
+        q_off, q_idx, q_val = sparse_queries
+        if _is_dev(q_off):
+            q_off = q_off.cpu().numpy()
+        if _is_dev(q_idx) != _is_dev(q_val):
+            raise ValueError("search_hybrid: the sparse queries' indices and values must both be NumPy arrays or both be device tensors")
+        q_off, q_idx, q_val, nqs = _csr(q_off, q_idx, q_val, "search_hybrid")
+        if nqs != nq:
+            raise ValueError("search_hybrid: %d dense and %d sparse queries" % (nq, nqs))
+        spec = (("ids", (nq, k), "int64"), ("score", (nq, k), "float32"), ("dense", (nq, k), "float32"), ("sparse", (nq, k), "float32"),
+                ("counts", (nq,), "int32"))
+        if out is None:
+            ids, score, dense, sparse, counts = _results("search_hybrid", spec, None, queries)
+            if not parts:
+                dense = sparse = None
+        else:
+            ids, score, dense, sparse, counts = out
+            given = tuple((a, s) for a, s in zip(out, spec) if a is not None)
+            # (a mixed set of NumPy and device buffers is the C ABI's to refuse, as in search)
+            _results("search_hybrid", tuple(s for _, s in given), tuple(a for a, _ in given), queries, one_kind=False)
+        self._keep["hybrid"] = (sparse_index, queries, q_off, q_idx, q_val)   # (device results: the call is still running when this returns)
+        nnz = _size(q_idx)
+        self._check(self.L.eps_index_search_hybrid(self.h, sparse_index.h, _ptr(queries), _ptr(q_off), _ptr(q_idx) if nnz else None,
+                                                   _ptr(q_val) if nnz else None, nq, k, float(w_dense), float(w_sparse), _ptr(ids), _ptr(score),
+                                                   _ptr(dense), _ptr(sparse), _ptr(counts)))
+        return ids, score, dense, sparse, counts
+
     def set_groups(self, keys):
         """eps_index_set_groups: one int64 key per row (NumPy, or a contiguous 1-D int64 device tensor); rows with equal keys form a group.  None
         forgets the groups.  After attach_rows / append_rows the keys must be set again."""
