@@ -41,6 +41,8 @@
  *                                   time on inverted lists built on request (eps_sparse_index_build_inverted), the same bits
  *   eps_index_search_hybrid         (new) the k rows with the smallest weighted sum of a dense and a sparse distance, over a dense handle and a
  *                                   sparse handle that hold the same records, in one fused pass; the reference has no relative
+ *   eps_binary_index_*              (new) a 1-bit-per-dimension field: the exact Hamming top-k of a table of packed bits, and the packing of
+ *                                   float signs into such bits; the reference has no relative
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -771,6 +773,52 @@ int32_t eps_sparse_index_get_inverted(eps_sparse_index* h, int64_t* col_offsets,
 int32_t eps_index_search_hybrid(eps_index* h, eps_sparse_index* s, const float* queries, const int64_t* q_offsets, const int32_t* q_indices,
                                 const float* q_values, int64_t nq, int32_t k, float w_dense, float w_sparse, int64_t* ids_out, float* score_out,
                                 float* dense_out, float* sparse_out, int32_t* counts_out);
+
+/* ---- Binary-vector fields: exact Hamming top-k on packed bits.  The reference has no such field type; what a caller had was every bit inflated
+ * to a +-1 float in an EUCLIDEAN eps_index (distance = 4 x Hamming) at 32 x the bytes.  A handle of its own kind: nothing of an eps_index or an
+ * eps_sparse_index applies to it.  Binary embeddings, sign-quantised first stages (the exact second stage is eps_index_search_among) and
+ * perceptual hashes are what it is for.
+ *
+ * Layout.  W = ceil(dim / 32) words per vector; bit j of a vector is bit j % 32 of word j / 32 (on a little-endian host: NumPy's
+ * packbits(bitorder="little") viewed as uint32).  Row r of a table starts at words + r * stride_words, stride_words >= W.  Bits of the last word at
+ * positions >= dim are ignored in rows and in queries and may hold anything; a table has no other validity condition, so nothing validates it.
+ * distance(row, query) = popcount((row ^ query) & mask_dim), an integer in [0, dim].  For query j the search returns the k smallest
+ * (distance, id) keys over the rows whose bit in the deleted bitset is clear; ties go to the smaller row.
+ *
+ * create: 1 <= dim <= 65536, else EPS_USER_ERROR; status codes and the no-CPU-fallback rule (EPS_INFRA_UNEXPECTED_ERROR without a gfx950 device)
+ * as eps_index_create.  A NULL handle: EPS_USER_ERROR from every call.
+ * attach_rows: host words are copied, device words are borrowed (the caller keeps them alive and unchanged); 0 <= n < 2^31, stride_words >= W
+ * else EPS_USER_ERROR.  Replaces any previous table and forgets the bitset.  The call synchronises the handle's stream.
+ * attach_signs: rows float[n][dim], host or device; bit j of a row is set iff rows[r][j] > 0.0f (NaN, -0 and +0 give a clear bit).  The bits are
+ * packed on the device into a table the handle owns; the floats are not kept.  The call synchronises.
+ * pack_signs: the same rule for x float[m][dim] -> words_out uint32[m][W] (pad bits clear), so that queries are quantised like the rows; both
+ * pointers host (the call synchronises) or both device (asynchronous on the handle's stream), a mixed pair is EPS_USER_ERROR.
+ * set_id_map / set_deleted: as eps_sparse_index_set_id_map / _set_deleted (host or device bits, nbytes >= ceil(n / 8) else EPS_USER_ERROR, NULL
+ * clears).  Int-column tests and filter programs are not served here: a caller folds them into the bitset.
+ * search: queries uint32[nq][W], contiguous.  1 <= k <= 1024 else EPS_USER_ERROR; nq = 0: EPS_OK, nothing touched; n = 0: counts 0.  ids_out
+ * [nq][k] and dist_out int32 [nq][k] ascending, counts_out [nq] (may be NULL); ids through the id map, unused slots -1 / INT32_MAX, counts =
+ * min(k, visible rows).  queries and the outputs are all host - the call synchronises - or all device - the call is asynchronous on the handle's
+ * stream and has no host synchronisation of its own; a mixed set or a NULL required buffer is EPS_USER_ERROR.
+ * One pass (csrc/binary.hip; plan: csrc/binary_host.hpp): one lane owns one row, its words stationary in registers eight at a time; the query
+ * words are wave-uniform scalar operands; a (row, query) word costs a v_xor_b32 and a v_bcnt_u32_b32.  A workgroup serves a tile of up to 32
+ * queries (32 / ceil(k / 64) of them, at least 4), so the table is read once per tile: n * W * 4 bytes.
+ * last_stats: dist_evals = n * nq, main_kernel_rows = n, main_kernel_queries = nq, main_kernel_bits = 1, main_kernel_launches, kernel_ms /
+ * main_kernel_ms from events; everything else 0. */
+typedef struct eps_binary_index eps_binary_index;
+int32_t eps_binary_index_create(int64_t dim, int32_t device, eps_binary_index** out);
+int32_t eps_binary_index_destroy(eps_binary_index* h);
+const char* eps_binary_index_last_error(const eps_binary_index* h);
+int32_t eps_binary_index_set_stream(eps_binary_index* h, void* hip_stream);
+int32_t eps_binary_index_synchronize(eps_binary_index* h);
+int32_t eps_binary_index_attach_rows(eps_binary_index* h, const uint32_t* words, int64_t n, int64_t stride_words);
+int32_t eps_binary_index_attach_signs(eps_binary_index* h, const float* rows, int64_t n);
+int32_t eps_binary_index_pack_signs(eps_binary_index* h, const float* x, int64_t m, uint32_t* words_out);
+int64_t eps_binary_index_row_count(const eps_binary_index* h);
+int32_t eps_binary_index_set_id_map(eps_binary_index* h, int64_t base, int64_t stride);
+int32_t eps_binary_index_set_deleted(eps_binary_index* h, const uint8_t* bits, int64_t nbytes);
+int32_t eps_binary_index_search(eps_binary_index* h, const uint32_t* queries, int64_t nq, int32_t k, int64_t* ids_out, int32_t* dist_out,
+                                int32_t* counts_out);
+int32_t eps_binary_index_last_stats(const eps_binary_index* h, eps_search_stats* out);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

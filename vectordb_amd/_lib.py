@@ -40,6 +40,9 @@ EXPORTS = [
     "eps_sparse_index_attach_csr", "eps_sparse_index_row_count", "eps_sparse_index_set_id_map", "eps_sparse_index_set_deleted", "eps_sparse_index_search",
     "eps_sparse_index_last_stats", "eps_sparse_index_build_inverted", "eps_sparse_index_drop_inverted", "eps_sparse_index_inverted_info",
     "eps_sparse_index_get_inverted", "eps_index_search_hybrid",
+    "eps_binary_index_create", "eps_binary_index_destroy", "eps_binary_index_last_error", "eps_binary_index_set_stream", "eps_binary_index_synchronize",
+    "eps_binary_index_attach_rows", "eps_binary_index_attach_signs", "eps_binary_index_pack_signs", "eps_binary_index_row_count",
+    "eps_binary_index_set_id_map", "eps_binary_index_set_deleted", "eps_binary_index_search", "eps_binary_index_last_stats",
 ]
 
 # Engine-selection switches of the library (eps_set_tuning, include/epsilla_gfx950.h).  The library itself reads no environment
@@ -273,6 +276,21 @@ def load():
     L.eps_sparse_index_drop_inverted.argtypes = [vp]
     L.eps_sparse_index_inverted_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     L.eps_sparse_index_get_inverted.argtypes = [vp, vp, vp, vp]
+    L.eps_binary_index_create.argtypes = [i64, i32, C.POINTER(vp)]
+    L.eps_binary_index_destroy.argtypes = [vp]
+    L.eps_binary_index_last_error.argtypes = [vp]
+    L.eps_binary_index_last_error.restype = C.c_char_p
+    L.eps_binary_index_set_stream.argtypes = [vp, vp]
+    L.eps_binary_index_synchronize.argtypes = [vp]
+    L.eps_binary_index_attach_rows.argtypes = [vp, vp, i64, i64]
+    L.eps_binary_index_attach_signs.argtypes = [vp, vp, i64]
+    L.eps_binary_index_pack_signs.argtypes = [vp, vp, i64, vp]
+    L.eps_binary_index_row_count.argtypes = [vp]
+    L.eps_binary_index_row_count.restype = i64
+    L.eps_binary_index_set_id_map.argtypes = [vp, i64, i64]
+    L.eps_binary_index_set_deleted.argtypes = [vp, vp, i64]
+    L.eps_binary_index_search.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.eps_binary_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     for name in EXPORTS:
         if getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = i32

@@ -64,6 +64,23 @@ static int32_t on_sparse(eps_sparse_index* h, F&& f) {
   }
 }
 
+// A binary-vector handle (eps_binary_index): the same rule.
+#define BIX(h) reinterpret_cast<eps::BinaryIndex*>(h)
+template <class F>
+static int32_t on_binary(eps_binary_index* h, F&& f) {
+  if (!h) return EPS_USER_ERROR;
+  eps::BinaryIndex* ix = BIX(h);
+  try {
+    return f(*ix);
+  } catch (const std::bad_alloc&) {
+    return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "out of host memory");
+  } catch (const std::exception& e) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, std::string("unexpected: ") + e.what());
+  } catch (...) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, "unexpected exception");
+  }
+}
+
 // The merges have no handle to keep a message in: a refusal names its reason on stderr, as a failed eps_index_create does.
 static int32_t merge_refused(const char* entry, const char* why, int32_t rc) {
   std::fprintf(stderr, "%s: %s\n", entry, why);
@@ -501,6 +518,65 @@ int32_t eps_index_search_hybrid(eps_index* h, eps_sparse_index* s, const float* 
   return on_single_device(h, "search_hybrid: single-device indices only (a sharded table is not served)", EPS_ERRCLASS_OTHER, [&](Index& ix) {
     return ix.search_hybrid(SIX(s)->view(), queries, q_offsets, q_indices, q_values, nq, k, w_dense, w_sparse, ids, score, dense, sparse, counts);
   });
+}
+
+// ---- binary-vector fields (binary_index.cpp; kernels: binary.hip)
+int32_t eps_binary_index_create(int64_t dim, int32_t device, eps_binary_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (eps::binary_create_refusal(dim)) return EPS_USER_ERROR;
+  try {
+    eps::BinaryIndex* ix = new eps::BinaryIndex(dim, device);
+    const int32_t rc = ix->init();
+    if (rc != EPS_OK) {
+      std::fprintf(stderr, "eps_binary_index_create: %s\n", ix->last_error());
+      delete ix;
+      return rc;
+    }
+    *out = reinterpret_cast<eps_binary_index*>(ix);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_binary_index_destroy(eps_binary_index* h) {
+  if (!h) return EPS_USER_ERROR;
+  try {
+    delete BIX(h);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+const char* eps_binary_index_last_error(const eps_binary_index* h) { return h ? reinterpret_cast<const eps::BinaryIndex*>(h)->last_error() : "null handle"; }
+int32_t eps_binary_index_set_stream(eps_binary_index* h, void* s) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.set_stream(s); });
+}
+int32_t eps_binary_index_synchronize(eps_binary_index* h) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.synchronize(); });
+}
+int32_t eps_binary_index_attach_rows(eps_binary_index* h, const uint32_t* words, int64_t n, int64_t stride_words) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.attach_rows(words, n, stride_words); });
+}
+int32_t eps_binary_index_attach_signs(eps_binary_index* h, const float* rows, int64_t n) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.attach_signs(rows, n); });
+}
+int32_t eps_binary_index_pack_signs(eps_binary_index* h, const float* x, int64_t m, uint32_t* words_out) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.pack_signs(x, m, words_out); });
+}
+int64_t eps_binary_index_row_count(const eps_binary_index* h) { return h ? reinterpret_cast<const eps::BinaryIndex*>(h)->row_count() : -1; }
+int32_t eps_binary_index_set_id_map(eps_binary_index* h, int64_t b, int64_t s) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.set_id_map(b, s); });
+}
+int32_t eps_binary_index_set_deleted(eps_binary_index* h, const uint8_t* bits, int64_t nbytes) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.set_deleted(bits, nbytes); });
+}
+int32_t eps_binary_index_search(eps_binary_index* h, const uint32_t* queries, int64_t nq, int32_t k, int64_t* ids, int32_t* dist, int32_t* counts) {
+  return on_binary(h, [&](eps::BinaryIndex& ix) { return ix.search(queries, nq, k, ids, dist, counts); });
+}
+int32_t eps_binary_index_last_stats(const eps_binary_index* h, eps_search_stats* out) {
+  if (!h || !out) return EPS_USER_ERROR;
+  return BIX(const_cast<eps_binary_index*>(h))->last_stats(out);
 }
 
 int32_t eps_set_tuning(const char* name, const char* value) {

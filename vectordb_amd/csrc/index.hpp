@@ -497,6 +497,48 @@ class SparseIndex {
   std::string err_;
 };
 
+// A binary-vector field behind eps_binary_index_* (binary_index.cpp; kernels: binary.hip; plan: binary_host.hpp): a table of packed bits in HBM, a
+// deleted bitset, an id map, and the exact Hamming scan.  A handle type of its own, as the sparse one.
+class BinaryIndex {
+ public:
+  BinaryIndex(int64_t dim, int device) : device_(device), dim_(dim), W_(binary_words(dim)) {}
+  ~BinaryIndex();
+  int32_t init();
+  int32_t set_stream(void* s);
+  int32_t synchronize();
+  int32_t attach_rows(const uint32_t* words, int64_t n, int64_t stride_words);
+  int32_t attach_signs(const float* rows, int64_t n);
+  int32_t pack_signs(const float* x, int64_t m, uint32_t* words_out);
+  int64_t row_count() const { return n_; }
+  int32_t set_id_map(int64_t base, int64_t stride);
+  int32_t set_deleted(const uint8_t* bits, int64_t nbytes);
+  int32_t search(const uint32_t* queries, int64_t nq, int32_t k, int64_t* ids_out, int32_t* dist_out, int32_t* counts_out);
+  int32_t last_stats(eps_search_stats* out);
+  const char* last_error() const { return err_.c_str(); }
+  int32_t fail(int32_t code, const std::string& msg) {
+    err_ = msg;
+    return code;
+  }
+  int32_t hip_fail(hipError_t e, const char* what);
+  int device_;
+
+ private:
+  // x float[m][dim], host or device -> bits at `words` (device, rows of `stride` words); host rows go through a staging buffer in slabs
+  int32_t pack_to(const float* x, bool x_dev, int64_t m, uint32_t* words, int64_t stride);
+  int64_t dim_, W_;
+  hipStream_t stream_ = nullptr;
+  bool own_stream_ = false;
+  DevBuf table_buf_;                 // an owned bit table (host words, attach_signs); a device table is borrowed
+  const uint32_t* rows_ = nullptr;
+  int64_t n_ = 0, stride_ = 0;
+  int64_t id_base_ = 0, id_stride_ = 1;
+  const uint8_t* d_deleted_ = nullptr;
+  DevBuf deleted_buf_, stage_buf_, q_buf_, partial_buf_, run_buf_, out_buf_;
+  hipEvent_t ev0_ = nullptr, ev1_ = nullptr, evk0_ = nullptr, evk1_ = nullptr;
+  eps_search_stats stats_{};
+  std::string err_;
+};
+
 // engines implemented in their own translation units
 // approx = true: no exact re-rank, the top-k is selected on the fp16 keys (kNN-graph construction), filters ignored
 // bits: operand width of the filter pass - 8 (int8 mirror; falls back to 16 where the table does not fit an 8-bit grid or the

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "among_host.hpp"
+#include "binary_host.hpp"
 #include "device_common.hpp"
 #include "diverse_host.hpp"
 #include "filters_host.hpp"
@@ -475,6 +476,27 @@ struct HybridArgs {
 void launch_hybrid_tiles(const HybridArgs& a, hipStream_t s);
 // the two terms of every key of a.run_keys, +inf where a slot is unused; nothing where both outputs are null
 void launch_hybrid_parts(const HybridArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- binary-vector scan (eps_binary_index_*; binary.hip, plan: binary_host.hpp)
+struct BinaryScanArgs {
+  const u32* rows;              // the bit table: row r starts at rows + r * stride
+  int64_t n, stride;
+  int W;                        // words of a vector, ceil(dim / 32)
+  u32 tail_mask;                // bits of word W - 1 that belong to the vector
+  int vec;                      // rows can be read in 16-byte pieces (stride % 4 == 0 and the table starts on 16 bytes)
+  const u32* queries;           // [nq][W]
+  int64_t nq;
+  int k;
+  const uint8_t* deleted;       // the deleted bitset, or null
+  BinaryPlan plan;
+  u64* partial;                 // [nq][plan.slices][k] per-wavefront sorted lists of (distance << 32 | row)
+};
+void launch_binary_scan(const BinaryScanArgs& a, hipStream_t s);
+// run_keys -> ids through the id map, int32 distances, counts; unused slots -1 / INT32_MAX
+void launch_binary_finalize(const u64* run_keys, int64_t nq, int k, int64_t id_base, int64_t id_stride, int64_t* ids, int32_t* dist, int32_t* counts,
+                            hipStream_t s);
+// bit j of row r of `words` (rows of `stride` words) = x[r][j] > 0.0f; bits of the last word at positions >= dim are clear
+void launch_binary_pack(const float* x, int64_t m, int64_t dim, u32* words, int64_t stride, hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch
