@@ -43,6 +43,8 @@
  *                                   sparse handle that hold the same records, in one fused pass; the reference has no relative
  *   eps_binary_index_*              (new) a 1-bit-per-dimension field: the exact Hamming top-k of a table of packed bits, and the packing of
  *                                   float signs into such bits; the reference has no relative
+ *   eps_byte_index_*                (new) a one-byte-per-dimension field, int8 or uint8: the exact int32 L2 / dot top-k on the matrix cores;
+ *                                   the reference has no relative
  *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
@@ -819,6 +821,46 @@ int32_t eps_binary_index_set_deleted(eps_binary_index* h, const uint8_t* bits, i
 int32_t eps_binary_index_search(eps_binary_index* h, const uint32_t* queries, int64_t nq, int32_t k, int64_t* ids_out, int32_t* dist_out,
                                 int32_t* counts_out);
 int32_t eps_binary_index_last_stats(const eps_binary_index* h, eps_search_stats* out);
+
+/* ---- Byte-vector fields: exact top-k over one-byte-per-dimension vectors, int8 or uint8, on the matrix cores.  The reference has no such field
+ * type; what a caller had was every byte widened to a float in an eps_index at 4 x the bytes, whose fp32 distances stop being exact integers from
+ * about dim = 260 for full-range bytes.  A handle of its own kind: nothing of an eps_index, an eps_sparse_index or an eps_binary_index applies to
+ * it.  int8 embeddings and uint8 descriptors are what it is for.
+ *
+ * create: 1 <= dim <= 4096; metric EPS_METRIC_EUCLIDEAN or EPS_METRIC_DOT_PRODUCT - EPS_METRIC_COSINE is not an integer rule and is refused;
+ * is_unsigned: 0 = every byte of rows and queries is an int8, else a uint8.  Else EPS_USER_ERROR, the reason on stderr.  Status codes and the
+ * no-CPU-fallback rule as eps_index_create.  A NULL handle: EPS_USER_ERROR from every call.
+ * Distances are int32 and exact: EUCLIDEAN sum (x_i - q_i)^2, DOT_PRODUCT -sum x_i q_i (255^2 * 4096 < 2^31).  For query j the search returns the k
+ * smallest (distance, id) keys over the rows whose bit in the deleted bitset is clear; ties go to the smaller row.
+ * attach_rows: row r starts at bytes + r * stride_bytes, stride_bytes >= dim, 0 <= n < 2^31, else EPS_USER_ERROR; host or device bytes.  The handle
+ * ALWAYS keeps a copy of its own in its stored form - rows padded to d_pad = ceil(dim / 64) * 64 bytes, unsigned bytes as b ^ 0x80, one int32 term
+ * per row: ceil(n / 64) * 64 * (d_pad + 4) bytes of HBM - so the caller's bytes are the caller's again when the call returns.  Replaces any previous
+ * table and forgets the bitset.  The call synchronises the handle's stream.
+ * set_id_map / set_deleted: as eps_binary_index_set_id_map / _set_deleted.  Int-column tests and filter programs are not served here.
+ * search: queries [nq][dim] bytes of the handle's signedness, contiguous.  1 <= k <= 1024 else EPS_USER_ERROR; nq = 0: EPS_OK, nothing touched;
+ * n = 0: counts 0.  ids_out [nq][k] and dist_out int32 [nq][k] ascending, counts_out [nq] (may be NULL); ids through the id map, unused slots -1 /
+ * INT32_MAX, counts = min(k, visible rows).  queries and the outputs are all host - the call synchronises - or all device - the call is
+ * asynchronous on the handle's stream; a mixed set or a NULL required buffer is EPS_USER_ERROR.
+ * One pass (csrc/byte.hip; plan and the terms: csrc/byte_host.hpp): v_mfma_i32_16x16x64_i8 gives the exact dot product of the stored bytes and
+ * row_term + query_term - (dot << shift) the distance; a workgroup serves a tile of up to 32 queries (k <= 64, d_pad <= 2048), else 16, 8 (k > 256)
+ * or 4 (k > 512), so the table is read once per tile: n * d_pad bytes.
+ * last_stats: dist_evals = n * nq, main_kernel_rows = n, main_kernel_queries = nq, main_kernel_bits = 8, main_kernel_launches, kernel_ms /
+ * main_kernel_ms from events; expansions = 100 * (live columns of a query tile) + (list registers per lane, KPL): the scan's form;
+ * filter_rows_all = rounds of 64 rows the wavefronts walked, all tiles together; rerank_rows = those of them that went through the hit path (a row
+ * could enter a list) instead of ending at the vote; everything else 0. */
+typedef struct eps_byte_index eps_byte_index;
+int32_t eps_byte_index_create(int64_t dim, int32_t metric, int32_t is_unsigned, int32_t device, eps_byte_index** out);
+int32_t eps_byte_index_destroy(eps_byte_index* h);
+const char* eps_byte_index_last_error(const eps_byte_index* h);
+int32_t eps_byte_index_set_stream(eps_byte_index* h, void* hip_stream);
+int32_t eps_byte_index_synchronize(eps_byte_index* h);
+int32_t eps_byte_index_attach_rows(eps_byte_index* h, const void* bytes, int64_t n, int64_t stride_bytes);
+int64_t eps_byte_index_row_count(const eps_byte_index* h);
+int32_t eps_byte_index_set_id_map(eps_byte_index* h, int64_t base, int64_t stride);
+int32_t eps_byte_index_set_deleted(eps_byte_index* h, const uint8_t* bits, int64_t nbytes);
+int32_t eps_byte_index_search(eps_byte_index* h, const void* queries, int64_t nq, int32_t k, int64_t* ids_out, int32_t* dist_out,
+                              int32_t* counts_out);
+int32_t eps_byte_index_last_stats(const eps_byte_index* h, eps_search_stats* out);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

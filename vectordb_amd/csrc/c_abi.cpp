@@ -81,6 +81,23 @@ static int32_t on_binary(eps_binary_index* h, F&& f) {
   }
 }
 
+// A byte-vector handle (eps_byte_index): the same rule.
+#define YIX(h) reinterpret_cast<eps::ByteIndex*>(h)
+template <class F>
+static int32_t on_byte(eps_byte_index* h, F&& f) {
+  if (!h) return EPS_USER_ERROR;
+  eps::ByteIndex* ix = YIX(h);
+  try {
+    return f(*ix);
+  } catch (const std::bad_alloc&) {
+    return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "out of host memory");
+  } catch (const std::exception& e) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, std::string("unexpected: ") + e.what());
+  } catch (...) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, "unexpected exception");
+  }
+}
+
 // The merges have no handle to keep a message in: a refusal names its reason on stderr, as a failed eps_index_create does.
 static int32_t merge_refused(const char* entry, const char* why, int32_t rc) {
   std::fprintf(stderr, "%s: %s\n", entry, why);
@@ -577,6 +594,62 @@ int32_t eps_binary_index_search(eps_binary_index* h, const uint32_t* queries, in
 int32_t eps_binary_index_last_stats(const eps_binary_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;
   return BIX(const_cast<eps_binary_index*>(h))->last_stats(out);
+}
+
+// ---- byte-vector fields (byte_index.cpp; kernels: byte.hip)
+int32_t eps_byte_index_create(int64_t dim, int32_t metric, int32_t is_unsigned, int32_t device, eps_byte_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (const char* why = eps::byte_create_refusal(dim, metric)) {
+    std::fprintf(stderr, "eps_byte_index_create: %s\n", why);
+    return EPS_USER_ERROR;
+  }
+  try {
+    eps::ByteIndex* ix = new eps::ByteIndex(dim, metric, is_unsigned, device);
+    const int32_t rc = ix->init();
+    if (rc != EPS_OK) {
+      std::fprintf(stderr, "eps_byte_index_create: %s\n", ix->last_error());
+      delete ix;
+      return rc;
+    }
+    *out = reinterpret_cast<eps_byte_index*>(ix);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_byte_index_destroy(eps_byte_index* h) {
+  if (!h) return EPS_USER_ERROR;
+  try {
+    delete YIX(h);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+const char* eps_byte_index_last_error(const eps_byte_index* h) { return h ? reinterpret_cast<const eps::ByteIndex*>(h)->last_error() : "null handle"; }
+int32_t eps_byte_index_set_stream(eps_byte_index* h, void* s) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.set_stream(s); });
+}
+int32_t eps_byte_index_synchronize(eps_byte_index* h) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.synchronize(); });
+}
+int32_t eps_byte_index_attach_rows(eps_byte_index* h, const void* bytes, int64_t n, int64_t stride_bytes) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.attach_rows(bytes, n, stride_bytes); });
+}
+int64_t eps_byte_index_row_count(const eps_byte_index* h) { return h ? reinterpret_cast<const eps::ByteIndex*>(h)->row_count() : -1; }
+int32_t eps_byte_index_set_id_map(eps_byte_index* h, int64_t b, int64_t s) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.set_id_map(b, s); });
+}
+int32_t eps_byte_index_set_deleted(eps_byte_index* h, const uint8_t* bits, int64_t nbytes) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.set_deleted(bits, nbytes); });
+}
+int32_t eps_byte_index_search(eps_byte_index* h, const void* queries, int64_t nq, int32_t k, int64_t* ids, int32_t* dist, int32_t* counts) {
+  return on_byte(h, [&](eps::ByteIndex& ix) { return ix.search(queries, nq, k, ids, dist, counts); });
+}
+int32_t eps_byte_index_last_stats(const eps_byte_index* h, eps_search_stats* out) {
+  if (!h || !out) return EPS_USER_ERROR;
+  return YIX(const_cast<eps_byte_index*>(h))->last_stats(out);
 }
 
 int32_t eps_set_tuning(const char* name, const char* value) {

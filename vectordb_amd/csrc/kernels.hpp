@@ -6,6 +6,7 @@
 
 #include "among_host.hpp"
 #include "binary_host.hpp"
+#include "byte_host.hpp"
 #include "device_common.hpp"
 #include "diverse_host.hpp"
 #include "filters_host.hpp"
@@ -497,6 +498,33 @@ void launch_binary_finalize(const u64* run_keys, int64_t nq, int k, int64_t id_b
                             hipStream_t s);
 // bit j of row r of `words` (rows of `stride` words) = x[r][j] > 0.0f; bits of the last word at positions >= dim are clear
 void launch_binary_pack(const float* x, int64_t m, int64_t dim, u32* words, int64_t stride, hipStream_t s);
+
+// ---------------------------------------------------------------- byte-vector scan (eps_byte_index_*; byte.hip, plan: byte_host.hpp)
+// src: m rows of `dim` bytes, `stride` bytes apart -> dst: m_pad >= m rows of d_pad = byte_pad(dim) stored bytes (b ^ 0x80 where is_unsigned, zeros in
+// the pad bytes and in the rows behind m) and term[m_pad] = byte_term(...) of each row (0 behind m).  is_query: the query's term rule
+void launch_byte_prepare(const uint8_t* src, int64_t m, int64_t m_pad, int64_t dim, int64_t stride, int metric, int is_unsigned, int is_query,
+                         signed char* dst, int32_t* term, hipStream_t s);
+struct ByteScanArgs {
+  const signed char* rows;      // the stored table: byte_pad_rows(n) rows of d_pad bytes, 16-byte aligned
+  const int32_t* row_term;      // [byte_pad_rows(n)]
+  int64_t n;
+  int d_pad;
+  int shift;                    // byte_dot_shift(metric)
+  const signed char* queries;   // [nq][d_pad] stored bytes
+  const int32_t* query_term;    // [nq]
+  int64_t nq;
+  int k;
+  const uint8_t* deleted;       // the deleted bitset, or null
+  BytePlan plan;
+  u64* partial;                 // [nq][plan.slices][k] per-wavefront sorted lists of ((u32)(distance + 2^31) << 32 | row)
+  u64* hit_rounds;              // one counter: rounds that went through the hit path (zeroed by the caller)
+};
+// once per handle (= per device): the scan forms' dynamic LDS allowance
+void byte_scan_allow_lds();
+void launch_byte_scan(const ByteScanArgs& a, hipStream_t s);
+// run_keys -> ids through the id map, int32 distances (the bias removed), counts; unused slots -1 / INT32_MAX
+void launch_byte_finalize(const u64* run_keys, int64_t nq, int k, int64_t id_base, int64_t id_stride, int64_t* ids, int32_t* dist, int32_t* counts,
+                          hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
 // a.dist != null: the radius form, else the select form (MergeRankArgs: merge_host.hpp); one launch
