@@ -45,7 +45,9 @@
  *                                   float signs into such bits; the reference has no relative
  *   eps_byte_index_*                (new) a one-byte-per-dimension field, int8 or uint8: the exact int32 L2 / dot top-k on the matrix cores;
  *                                   the reference has no relative
- *   eps_normalize_rows              Normalize (db/vector.cpp:60-69) and the insert-time normalisation
+ *   eps_half_index_*                (new) an fp16 or bf16 field: the fp32 L2 / dot / cosine top-k on the matrix cores with thresholds seeded
+ *                                   from a prefix of the table, and the rounding of floats to such halves; the reference has no relative
+ *   eps_normalize_rows             Normalize (db/vector.cpp:60-69) and the insert-time normalisation
  *                                   (db/table_segment_mvp.cpp:574-587)
  *   eps_merge_topk                  (new) merges per-shard top-k lists after the RCCL all-gather
  *   eps_merge_range / _packed       (new) joins the answers G shards gave to one eps_index_search_range into the unsharded table's answer
@@ -861,6 +863,61 @@ int32_t eps_byte_index_set_deleted(eps_byte_index* h, const uint8_t* bits, int64
 int32_t eps_byte_index_search(eps_byte_index* h, const void* queries, int64_t nq, int32_t k, int64_t* ids_out, int32_t* dist_out,
                               int32_t* counts_out);
 int32_t eps_byte_index_last_stats(const eps_byte_index* h, eps_search_stats* out);
+
+/* ---- Half-vector fields: top-k over fp16 or bf16 vectors on the matrix cores.  The reference has no such field type; what a caller had was every
+ * element widened to a float in an eps_index at twice the bytes (10M x 768: 30.7 GB against 15.4 GB) for rows that carry no more information.  A
+ * handle of its own kind: nothing of an eps_index, an eps_sparse_index, an eps_binary_index or an eps_byte_index applies to it.
+ *
+ * create: 1 <= dim <= 4096; metric EPS_METRIC_EUCLIDEAN, EPS_METRIC_COSINE or EPS_METRIC_DOT_PRODUCT; is_bf16: 0 = every element of rows and
+ * queries is an IEEE fp16, else a bf16.  Else EPS_USER_ERROR, the reason on stderr.  Status codes and the no-CPU-fallback rule as
+ * eps_index_create.  A NULL handle: EPS_USER_ERROR from every call.
+ * The rule.  Distances are fp32.  x.q is the matrix cores' fp32 sum of the products, which v_mfma_f32_16x16x32_f16 / _bf16 take exactly (an
+ * fp16 x fp16 product has 22 significant bits, a bf16 x bf16 product 16), K-steps of 32 elements in ascending order: only the sums round.  |x|^2
+ * (one fp32 term per row, written at attach) and |q|^2 (per query, per call) come from one fixed order: 64 chains of fmas over elements l, l + 64,
+ * ..., added by an xor butterfly with offsets 1 .. 32.  EUCLIDEAN: t = (|x|^2 + |q|^2) - 2 x.q, 0 where t < 0; DOT_PRODUCT: -x.q; COSINE: 1 - x.q
+ * (normalising is the caller's job).  A row's distance is computed by one expression wherever it is computed, so one row has one value in a call.
+ * Against an fp64 evaluation of the same halves a distance is within gamma'(dim + 4) * mag, gamma'(m) = m u' / (1 - m u'), u' = 2^-23, mag = sum
+ * |x q| (EUCLIDEAN: sum x^2 + sum q^2 + 2 sum |x q|); on tables whose sums are integers below 2^24 it is that value bit for bit.  For query j the
+ * search returns the k smallest (distance, id) keys over the rows whose bit in the deleted bitset is clear; ties go to the smaller row; a NaN
+ * distance orders behind +inf, as in eps_index_search.  A row with an infinite element has a NaN EUCLIDEAN distance here (inf - inf), where the
+ * difference form of eps_index_search gives +inf.  Subnormal fp16 inputs: whether the matrix cores read them or flush them is the hardware's
+ * handling and unspecified until a later change measures it.
+ * attach_rows: row r starts at halves + r * stride_elems elements, stride_elems >= dim, 0 <= n < 2^31, else EPS_USER_ERROR; host or device.  The
+ * handle ALWAYS keeps a copy of its own in its stored form - rows padded with zeros to d_pad = ceil(dim / 32) * 32 elements, the table to whole
+ * rounds of 64 rows, one fp32 norm term per row (0 for the two dot metrics): ceil(n / 64) * 64 * (2 d_pad + 4) bytes of HBM - so the caller's
+ * rows are the caller's again when the call returns.  Replaces any previous table and forgets the bitset.  The call synchronises the stream.
+ * attach_floats: the same from contiguous float rows [n][dim], each element rounded to the handle's type on the device: to nearest, ties to
+ * even, a NaN stays a NaN, overflow goes to infinity.  convert_floats: the same rounding for x [m][dim] floats into halves_out [m][dim] - what
+ * queries need; both host (the call synchronises) or both device (asynchronous on the handle's stream), else EPS_USER_ERROR.
+ * set_id_map / set_deleted: as eps_binary_index_set_id_map / _set_deleted.  Int-column tests and filter programs are not served here.
+ * search: queries [nq][dim] halves of the handle's type, contiguous.  1 <= k <= 1024 else EPS_USER_ERROR; nq = 0: EPS_OK, nothing touched;
+ * n = 0: counts 0.  ids_out [nq][k] and dist_out float [nq][k] ascending, counts_out [nq] (may be NULL); ids through the id map, unused slots -1 /
+ * +inf, counts = min(k, visible rows).  queries and the outputs are all host - the call synchronises - or all device - the call is asynchronous
+ * on the handle's stream with no host synchronisation; a mixed set or a NULL required buffer is EPS_USER_ERROR.
+ * The scan (csrc/half.hip; plan, rounding and seed rule: csrc/half_host.hpp): a workgroup serves a tile of up to 64 queries (k <= 64, d_pad <=
+ * 1024), 32 (k <= 128, d_pad <= 2048), else 16, 8 (k > 256) or 4 (k > 512), so the table is read once per tile: n * 2 d_pad bytes.  A table of
+ * 32768 rows and more is scanned with SEEDED thresholds: a first launch takes the top-k of a prefix (a sixteenth of the table, at least 4096 and
+ * 8 k rows) and its k-th distance opens every slice of the main launch instead of an open threshold; the answer is the same.
+ * last_stats: dist_evals = (n + prefix rows) * nq, main_kernel_rows = n, main_kernel_queries = nq, main_kernel_bits = 16, main_kernel_launches,
+ * kernel_ms / main_kernel_ms (the main launch) from events; expansions = 100 * (live columns of a query tile) + (list registers per lane, KPL);
+ * filter_rows_all = rounds of 64 rows the main launch's wavefronts walked, all tiles together; rerank_rows = those of them that went through the
+ * hit path.  Three fields the byte handle leaves 0: overflow_queries = 1 if the thresholds were seeded, i8_folded = rows of the prefix,
+ * i8_declined = hit rounds of the seed launch (whose slices all start open).  Everything else 0. */
+typedef struct eps_half_index eps_half_index;
+int32_t eps_half_index_create(int64_t dim, int32_t metric, int32_t is_bf16, int32_t device, eps_half_index** out);
+int32_t eps_half_index_destroy(eps_half_index* h);
+const char* eps_half_index_last_error(const eps_half_index* h);
+int32_t eps_half_index_set_stream(eps_half_index* h, void* hip_stream);
+int32_t eps_half_index_synchronize(eps_half_index* h);
+int32_t eps_half_index_attach_rows(eps_half_index* h, const void* halves, int64_t n, int64_t stride_elems);
+int32_t eps_half_index_attach_floats(eps_half_index* h, const float* rows, int64_t n);
+int32_t eps_half_index_convert_floats(eps_half_index* h, const float* x, int64_t m, void* halves_out);
+int64_t eps_half_index_row_count(const eps_half_index* h);
+int32_t eps_half_index_set_id_map(eps_half_index* h, int64_t base, int64_t stride);
+int32_t eps_half_index_set_deleted(eps_half_index* h, const uint8_t* bits, int64_t nbytes);
+int32_t eps_half_index_search(eps_half_index* h, const void* queries, int64_t nq, int32_t k, int64_t* ids_out, float* dist_out,
+                              int32_t* counts_out);
+int32_t eps_half_index_last_stats(const eps_half_index* h, eps_search_stats* out);
 
 /* in-place L2 normalisation of float[n][dim] (host or device). only_if_nonzero = 1 reproduces the
  * insert path (sum > 1e-10), 0 the query path (unconditional). */

@@ -6,8 +6,9 @@ from .index import (ANNGraphSegment, Exchange, FLAT_AUTO, FLAT_MFMA, FLAT_MFMA_I
 from .sparse_index import GpuSparseIndex
 from .binary_index import GpuBinaryIndex
 from .byte_index import GpuByteIndex
+from .half_index import GpuHalfIndex
 from ._lib import EpsillaError, set_tuning  # noqa: F401
 
-__all__ = ["GpuSparseIndex", "GpuBinaryIndex", "GpuByteIndex","ANNGraphSegment", "Exchange", "VecSearchExecutor", "GetDistFunc", "GpuIndex", "normalize_rows", "merge_topk", "merge_topk_packed", "traversal_gather_bytes",
+__all__ = ["GpuSparseIndex", "GpuBinaryIndex", "GpuByteIndex", "GpuHalfIndex", "ANNGraphSegment", "Exchange", "VecSearchExecutor", "GetDistFunc", "GpuIndex", "normalize_rows", "merge_topk", "merge_topk_packed", "traversal_gather_bytes",
            "merge_range", "merge_range_packed", "merge_select", "range_pack_bytes", "search_range_shards", "select_shards", "multi_matches",
            "MODE_REFERENCE", "MODE_FLAT", "MODE_GRAPH", "FLAT_AUTO", "FLAT_STREAM", "FLAT_MFMA", "FLAT_MFMA_I8", "EpsillaError", "set_tuning"]

@@ -46,6 +46,9 @@ EXPORTS = [
     "eps_byte_index_create", "eps_byte_index_destroy", "eps_byte_index_last_error", "eps_byte_index_set_stream", "eps_byte_index_synchronize",
     "eps_byte_index_attach_rows", "eps_byte_index_row_count", "eps_byte_index_set_id_map", "eps_byte_index_set_deleted", "eps_byte_index_search",
     "eps_byte_index_last_stats",
+    "eps_half_index_create", "eps_half_index_destroy", "eps_half_index_last_error", "eps_half_index_set_stream", "eps_half_index_synchronize",
+    "eps_half_index_attach_rows", "eps_half_index_attach_floats", "eps_half_index_convert_floats", "eps_half_index_row_count",
+    "eps_half_index_set_id_map", "eps_half_index_set_deleted", "eps_half_index_search", "eps_half_index_last_stats",
 ]
 
 # Engine-selection switches of the library (eps_set_tuning, include/epsilla_gfx950.h).  The library itself reads no environment
@@ -307,6 +310,21 @@ def load():
     L.eps_byte_index_set_deleted.argtypes = [vp, vp, i64]
     L.eps_byte_index_search.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.eps_byte_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
+    L.eps_half_index_create.argtypes = [i64, i32, i32, i32, C.POINTER(vp)]
+    L.eps_half_index_destroy.argtypes = [vp]
+    L.eps_half_index_last_error.argtypes = [vp]
+    L.eps_half_index_last_error.restype = C.c_char_p
+    L.eps_half_index_set_stream.argtypes = [vp, vp]
+    L.eps_half_index_synchronize.argtypes = [vp]
+    L.eps_half_index_attach_rows.argtypes = [vp, vp, i64, i64]
+    L.eps_half_index_attach_floats.argtypes = [vp, vp, i64]
+    L.eps_half_index_convert_floats.argtypes = [vp, vp, i64, vp]
+    L.eps_half_index_row_count.argtypes = [vp]
+    L.eps_half_index_row_count.restype = i64
+    L.eps_half_index_set_id_map.argtypes = [vp, i64, i64]
+    L.eps_half_index_set_deleted.argtypes = [vp, vp, i64]
+    L.eps_half_index_search.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.eps_half_index_last_stats.argtypes = [vp, C.POINTER(SearchStats)]
     for name in EXPORTS:
         if getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = i32

@@ -12,12 +12,13 @@ OBJ = os.path.join(OUT, "obj")
 LIB = os.path.join(OUT, "libepsilla_gfx950.so")
 SOURCES = ["index.cpp", "index_calls.cpp", "c_abi.cpp", "shard_group.cpp", "exchange.cpp", "flat_kernels.hip", "traverse.hip", "mfma_filter.hip", "one_pass.hip",
            "mirror_build.hip", "graph_build.hip", "select.hip", "range.hip", "merge_lists.hip", "among.hip", "filters.hip", "groups.hip", "group_rows.hip", "multi.hip", "diverse.hip", "sparse.hip", "sparse_inverted.hip", "sparse_index.cpp", "hybrid.hip", "binary.hip", "binary_index.cpp",
-           "byte.hip", "byte_index.cpp"]
+           "byte.hip", "byte_index.cpp", "half.hip", "half_index.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(os.path.dirname(HERE), "include")]
 # per source, on top of FLAGS.  filters.hip: new units are built without packed fp32 arithmetic (the same bits lane by lane; scalar fmas only)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"filters.hip": NO_PACKED_FP32, "hybrid.hip": NO_PACKED_FP32, "binary.hip": NO_PACKED_FP32, "byte.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"filters.hip": NO_PACKED_FP32, "hybrid.hip": NO_PACKED_FP32, "binary.hip": NO_PACKED_FP32, "byte.hip": NO_PACKED_FP32,
+               "half.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

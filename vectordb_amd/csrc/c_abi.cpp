@@ -98,6 +98,23 @@ static int32_t on_byte(eps_byte_index* h, F&& f) {
   }
 }
 
+// A half-vector handle (eps_half_index): the same rule.
+#define HIX(h) reinterpret_cast<eps::HalfIndex*>(h)
+template <class F>
+static int32_t on_half(eps_half_index* h, F&& f) {
+  if (!h) return EPS_USER_ERROR;
+  eps::HalfIndex* ix = HIX(h);
+  try {
+    return f(*ix);
+  } catch (const std::bad_alloc&) {
+    return ix->fail(EPS_INFRA_UNEXPECTED_ERROR, "out of host memory");
+  } catch (const std::exception& e) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, std::string("unexpected: ") + e.what());
+  } catch (...) {
+    return ix->fail(EPS_DB_UNEXPECTED_ERROR, "unexpected exception");
+  }
+}
+
 // The merges have no handle to keep a message in: a refusal names its reason on stderr, as a failed eps_index_create does.
 static int32_t merge_refused(const char* entry, const char* why, int32_t rc) {
   std::fprintf(stderr, "%s: %s\n", entry, why);
@@ -650,6 +667,68 @@ int32_t eps_byte_index_search(eps_byte_index* h, const void* queries, int64_t nq
 int32_t eps_byte_index_last_stats(const eps_byte_index* h, eps_search_stats* out) {
   if (!h || !out) return EPS_USER_ERROR;
   return YIX(const_cast<eps_byte_index*>(h))->last_stats(out);
+}
+
+// ---- half-vector fields (half_index.cpp; kernels: half.hip)
+int32_t eps_half_index_create(int64_t dim, int32_t metric, int32_t is_bf16, int32_t device, eps_half_index** out) {
+  if (!out) return EPS_USER_ERROR;
+  *out = nullptr;
+  if (const char* why = eps::half_create_refusal(dim, metric)) {
+    std::fprintf(stderr, "eps_half_index_create: %s\n", why);
+    return EPS_USER_ERROR;
+  }
+  try {
+    eps::HalfIndex* ix = new eps::HalfIndex(dim, metric, is_bf16, device);
+    const int32_t rc = ix->init();
+    if (rc != EPS_OK) {
+      std::fprintf(stderr, "eps_half_index_create: %s\n", ix->last_error());
+      delete ix;
+      return rc;
+    }
+    *out = reinterpret_cast<eps_half_index*>(ix);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+int32_t eps_half_index_destroy(eps_half_index* h) {
+  if (!h) return EPS_USER_ERROR;
+  try {
+    delete HIX(h);
+    return EPS_OK;
+  } catch (...) {
+    return map_exception(nullptr);
+  }
+}
+const char* eps_half_index_last_error(const eps_half_index* h) { return h ? reinterpret_cast<const eps::HalfIndex*>(h)->last_error() : "null handle"; }
+int32_t eps_half_index_set_stream(eps_half_index* h, void* s) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.set_stream(s); });
+}
+int32_t eps_half_index_synchronize(eps_half_index* h) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.synchronize(); });
+}
+int32_t eps_half_index_attach_rows(eps_half_index* h, const void* halves, int64_t n, int64_t stride_elems) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.attach_rows(halves, n, stride_elems); });
+}
+int32_t eps_half_index_attach_floats(eps_half_index* h, const float* rows, int64_t n) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.attach_floats(rows, n); });
+}
+int32_t eps_half_index_convert_floats(eps_half_index* h, const float* x, int64_t m, void* halves_out) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.convert_floats(x, m, halves_out); });
+}
+int64_t eps_half_index_row_count(const eps_half_index* h) { return h ? reinterpret_cast<const eps::HalfIndex*>(h)->row_count() : -1; }
+int32_t eps_half_index_set_id_map(eps_half_index* h, int64_t b, int64_t s) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.set_id_map(b, s); });
+}
+int32_t eps_half_index_set_deleted(eps_half_index* h, const uint8_t* bits, int64_t nbytes) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.set_deleted(bits, nbytes); });
+}
+int32_t eps_half_index_search(eps_half_index* h, const void* queries, int64_t nq, int32_t k, int64_t* ids, float* dist, int32_t* counts) {
+  return on_half(h, [&](eps::HalfIndex& ix) { return ix.search(queries, nq, k, ids, dist, counts); });
+}
+int32_t eps_half_index_last_stats(const eps_half_index* h, eps_search_stats* out) {
+  if (!h || !out) return EPS_USER_ERROR;
+  return HIX(const_cast<eps_half_index*>(h))->last_stats(out);
 }
 
 int32_t eps_set_tuning(const char* name, const char* value) {

@@ -579,6 +579,49 @@ class ByteIndex {
   std::string err_;
 };
 
+// A half-vector field behind eps_half_index_* (half_index.cpp; kernels: half.hip; plan, rounding and seed rule: half_host.hpp): a table of fp16 or
+// bf16 vectors in its stored form in HBM - always a copy the handle owns, rows padded to whole K-steps, one fp32 norm term per row - a deleted
+// bitset, an id map, and the matrix-core scan with seeded thresholds.  A handle type of its own, as the byte one.
+class HalfIndex {
+ public:
+  HalfIndex(int64_t dim, int metric, int is_bf16, int device)
+      : device_(device), dim_(dim), d_pad_(half_pad(dim)), metric_(metric), bf16_(is_bf16 ? 1 : 0) {}
+  ~HalfIndex();
+  int32_t init();
+  int32_t set_stream(void* s);
+  int32_t synchronize();
+  int32_t attach_rows(const void* halves, int64_t n, int64_t stride_elems) { return attach(halves, n, stride_elems, 0); }
+  int32_t attach_floats(const float* rows, int64_t n) { return attach(rows, n, dim_, 1); }
+  int32_t convert_floats(const float* x, int64_t m, void* halves_out);
+  int64_t row_count() const { return n_; }
+  int32_t set_id_map(int64_t base, int64_t stride);
+  int32_t set_deleted(const uint8_t* bits, int64_t nbytes);
+  int32_t search(const void* queries, int64_t nq, int32_t k, int64_t* ids_out, float* dist_out, int32_t* counts_out);
+  int32_t last_stats(eps_search_stats* out);
+  const char* last_error() const { return err_.c_str(); }
+  int32_t fail(int32_t code, const std::string& msg) {
+    err_ = msg;
+    return code;
+  }
+  int32_t hip_fail(hipError_t e, const char* what);
+  int device_;
+
+ private:
+  int32_t attach(const void* src, int64_t n, int64_t stride_elems, int src_float);
+  int64_t dim_, d_pad_;
+  int metric_, bf16_;
+  hipStream_t stream_ = nullptr;
+  bool own_stream_ = false;
+  DevBuf table_buf_, term_buf_;      // half_pad_rows(n) stored rows of d_pad halves and their norm terms
+  int64_t n_ = 0;
+  int64_t id_base_ = 0, id_stride_ = 1;
+  const uint8_t* d_deleted_ = nullptr;
+  DevBuf deleted_buf_, stage_buf_, q_buf_, qterm_buf_, seed_buf_, partial_buf_, run_buf_, out_buf_, hit_buf_;   // hit_buf_: two counters, main pass and seed pass
+  hipEvent_t ev0_ = nullptr, ev1_ = nullptr, evk0_ = nullptr, evk1_ = nullptr;
+  eps_search_stats stats_{};
+  std::string err_;
+};
+
 // engines implemented in their own translation units
 // approx = true: no exact re-rank, the top-k is selected on the fp16 keys (kNN-graph construction), filters ignored
 // bits: operand width of the filter pass - 8 (int8 mirror; falls back to 16 where the table does not fit an 8-bit grid or the

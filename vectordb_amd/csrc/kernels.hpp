@@ -7,6 +7,7 @@
 #include "among_host.hpp"
 #include "binary_host.hpp"
 #include "byte_host.hpp"
+#include "half_host.hpp"
 #include "device_common.hpp"
 #include "diverse_host.hpp"
 #include "filters_host.hpp"
@@ -524,6 +525,39 @@ void byte_scan_allow_lds();
 void launch_byte_scan(const ByteScanArgs& a, hipStream_t s);
 // run_keys -> ids through the id map, int32 distances (the bias removed), counts; unused slots -1 / INT32_MAX
 void launch_byte_finalize(const u64* run_keys, int64_t nq, int k, int64_t id_base, int64_t id_stride, int64_t* ids, int32_t* dist, int32_t* counts,
+                          hipStream_t s);
+
+// ---------------------------------------------------------------- half-vector scan (eps_half_index_*; half.hip, plan and rounding: half_host.hpp)
+// out[i] = x[i] rounded to nearest even to fp16 or bf16 (half_from_float_bits)
+void launch_half_convert(const float* x, int64_t count, int is_bf16, uint16_t* out, hipStream_t s);
+// src: m rows of `dim` halves (src_float: floats, rounded as launch_half_convert rounds), `stride` elements apart -> dst: m_pad >= m rows of
+// d_pad = half_pad(dim) halves (zeros in the pad elements and in the rows behind m) and term[m_pad] = the row's fp32 |x|^2 under EUCLIDEAN, else 0
+void launch_half_prepare(const void* src, int src_float, int64_t m, int64_t m_pad, int64_t dim, int64_t stride, int metric, int is_bf16, uint16_t* dst,
+                         float* term, hipStream_t s);
+struct HalfScanArgs {
+  const uint16_t* rows;         // the stored table: half_pad_rows(table rows) rows of d_pad halves, 16-byte aligned
+  const float* row_term;        // [half_pad_rows(table rows)]
+  int64_t n;                    // rows this launch scans: the table, or the seed pass's prefix of it
+  int d_pad;
+  int metric;
+  int is_bf16;
+  const uint16_t* queries;      // [nq][d_pad] stored halves
+  const float* query_term;      // [nq]
+  int64_t nq;
+  int k;
+  const uint8_t* deleted;       // the deleted bitset, or null
+  const u32* seed;              // [nq] exclusive bounds on a key's high word every slice starts from (half_seed_kernel), or null: open
+  HalfPlan plan;                // half_plan(n, ...)
+  u64* partial;                 // [nq][plan.slices][k] per-wavefront sorted lists of float keys
+  u64* hit_rounds;              // one counter: rounds that went through the hit path (zeroed by the caller)
+};
+// once per handle (= per device): the scan forms' dynamic LDS allowance
+void half_scan_allow_lds();
+void launch_half_scan(const HalfScanArgs& a, hipStream_t s);
+// bound[q] from the k-th key of run_keys[q][k], the top-k of the prefix
+void launch_half_seed(const u64* run_keys, int64_t nq, int k, u32* bound, hipStream_t s);
+// run_keys -> ids through the id map, fp32 distances, counts; unused slots -1 / +inf
+void launch_half_finalize(const u64* run_keys, int64_t nq, int k, int64_t id_base, int64_t id_stride, int64_t* ids, float* dist, int32_t* counts,
                           hipStream_t s);
 
 // ---------------------------------------------------------------- windowed merge of sorted lists by rank (eps_merge_range, eps_merge_select; merge_lists.hip)
