@@ -880,8 +880,8 @@ int32_t eps_byte_index_last_stats(const eps_byte_index* h, eps_search_stats* out
  * |x q| (EUCLIDEAN: sum x^2 + sum q^2 + 2 sum |x q|); on tables whose sums are integers below 2^24 it is that value bit for bit.  For query j the
  * search returns the k smallest (distance, id) keys over the rows whose bit in the deleted bitset is clear; ties go to the smaller row; a NaN
  * distance orders behind +inf, as in eps_index_search.  A row with an infinite element has a NaN EUCLIDEAN distance here (inf - inf), where the
- * difference form of eps_index_search gives +inf.  Subnormal fp16 inputs: whether the matrix cores read them or flush them is the hardware's
- * handling and unspecified until a later change measures it.
+ * difference form of eps_index_search gives +inf.  Subnormal fp16 inputs are read as their values, in the dot products as in the norm
+ * terms (measured on an MI355X: nothing is flushed to zero).
  * attach_rows: row r starts at halves + r * stride_elems elements, stride_elems >= dim, 0 <= n < 2^31, else EPS_USER_ERROR; host or device.  The
  * handle ALWAYS keeps a copy of its own in its stored form - rows padded with zeros to d_pad = ceil(dim / 32) * 32 elements, the table to whole
  * rounds of 64 rows, one fp32 norm term per row (0 for the two dot metrics): ceil(n / 64) * 64 * (2 d_pad + 4) bytes of HBM - so the caller's

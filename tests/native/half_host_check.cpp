@@ -119,10 +119,49 @@ static void plans() {
         }
 }
 
+// The shapes at which a slice walks more than one round (tests/half_walk_ref.py: SHAPES; tests/test_gpu_half_rounds.py runs them): the caps bind
+// exactly as that table says.  A change of a cap or of the seed rule fails here instead of letting those tests fall back to one round per slice
+static void long_slices() {
+  struct Shape {
+    int64_t n, dim, nq;
+    int k, cols, kpl, nb;
+    int64_t tiles, slices, rows_per_slice, seed_rows, seed_slices, seed_rows_per_slice;
+  };
+  const Shape shapes[] = {
+      {32767, 40, 2053, 10, 64, 1, 4, 33, 248, 192, 0, 0, 0},        // R1: 3 rounds; slices from 171 on are empty; the last tile has 5 queries
+      {40000, 40, 2053, 10, 64, 1, 4, 33, 248, 192, 4096, 64, 64},   // R1s
+      {60000, 40, 5, 1024, 4, 16, 1, 2, 256, 256, 8192, 128, 64},    // R2: 4 rounds, the merge's cap; the 8 k rule
+      {40000, 40, 300, 1024, 4, 16, 1, 75, 108, 384, 8192, 108, 128},   // R3: 6 rounds; the seed pass walks two
+      {15000, 40, 2060, 129, 16, 4, 1, 129, 60, 256, 0, 0, 0},       // R4
+      {24000, 40, 2060, 65, 32, 2, 2, 65, 124, 256, 0, 0, 0},        // R5
+      {24000, 1056, 2060, 10, 32, 1, 2, 65, 124, 256, 0, 0, 0},      // R6: NB = 2 by LDS
+      {15000, 2080, 2060, 10, 16, 1, 1, 129, 60, 256, 0, 0, 0},      // R7: NB = 1 by LDS
+      {12000, 40, 2060, 257, 8, 8, 1, 258, 28, 448, 0, 0, 0},        // R8: 7 rounds
+  };
+  for (const Shape& s : shapes) {
+    const HalfPlan p = half_plan(s.n, s.dim, s.nq, s.k);
+    CHECK(p.cols == s.cols && p.kpl == s.kpl && p.nb == s.nb && p.tiles == s.tiles && p.launches == 1);
+    CHECK(p.slices == s.slices && p.rows_per_slice == s.rows_per_slice && p.rows_per_slice > HALF_WAVE_ROWS);
+    CHECK(p.rounds == (s.n + 63) / 64 * s.tiles);
+    const int64_t sr = half_seed_rows(s.n, s.dim, s.nq, s.k);
+    CHECK(sr == s.seed_rows);
+    if (sr > 0) {
+      const HalfPlan q = half_plan(sr, s.dim, s.nq, s.k);
+      CHECK(q.slices == s.seed_slices && q.rows_per_slice == s.seed_rows_per_slice && q.cols == s.cols && q.kpl == s.kpl && q.tiles == s.tiles);
+    }
+  }
+  int64_t b = -1, e = -1;   // R1's last non-empty slice is ragged, the next one empty
+  half_slice_rows(192, 32767, 170, &b, &e);
+  CHECK(b == 32640 && e == 32767);
+  half_slice_rows(192, 32767, 171, &b, &e);
+  CHECK(b == 32767 && e == 32767);
+}
+
 int main() {
   rounding();
   layout();
   plans();
+  long_slices();
   if (failures) printf("half_host_check: %d check(s) failed\n", failures);
   else printf("half_host_check OK\n");
   return failures != 0;

@@ -10,8 +10,8 @@
 // half_distance() below is that expression and the only place a distance is computed - the threshold test, the offered key and the seed pass all
 // go through it - so one row has one value in a call.  Order is (distance, row) ascending on device_common.hpp's float keys: a NaN distance orders
 // behind +inf, as in the flat search.  A row with an infinite element has |x|^2 = inf and x.q = +-inf or NaN: its EUCLIDEAN distance is a NaN here
-// (the flat search's difference form gives +inf); both order behind every number.  Subnormal fp16 inputs: whether the matrix cores read or flush
-// them is the hardware's handling and unspecified here until a later change measures it.
+// (the flat search's difference form gives +inf); both order behind every number.  Subnormal fp16 inputs: the matrix cores read them
+// as their values, as the norm terms do - measured on an MI355X (tests/test_gpu_half_rounds.py: rows of integers x 2^-24 answer bit for bit).
 //
 // half_convert_kernel   float -> half, round to nearest even on the bits (half_host.hpp's half_from_float_bits).
 // half_prepare_kernel   the stored form, at attach and per batch of queries: rows of halves (or of floats, rounded as above) padded with zeros to
